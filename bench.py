@@ -8,6 +8,10 @@ CLIP-L/G prompt encode -> 20 Euler-a steps with cond/uncond batched (UNet batch 
 of the exact architecture (no network / checkpoints available); rank 0's weights are broadcast to
 every rank (R3). Timed region = exactly K steps bracketed by barrier + device synchronize; the
 reported time is the MAX over ranks. Prints one JSON line on rank 0.
+
+A plain run does nothing beyond set-up, warm-up, the K timed steps and the result line (``ms_per_step`` =
+timed seconds * 1000 / K). ``--dump-outputs DIR`` also writes the last timed step's images as
+``DIR/images.npy``; ``--full`` is where secondary measurements belong (none today).
 """
 from __future__ import annotations
 
@@ -44,6 +48,26 @@ def _labels(args):
     return metric, data, model
 
 
+DUMP_MAX_ELEMS = 8 * 1024 * 1024     # float32 elements written per array (32 MiB)
+
+
+def _dump_outputs(out_dir, arrays):
+    """--dump-outputs: write what the last timed step returned as ``<out_dir>/<name>.npy`` (float32). An
+    array of more than DUMP_MAX_ELEMS elements is written as a fixed sample of its flattened elements (the
+    same seeded indices in every run and build, in ascending order), so two runs compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_MAX_ELEMS))
+            a = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -69,7 +93,18 @@ def main():
                     help="time the product path: a text-to-image workflow JSON through validate_prompt + "
                          "PromptExecutor (CLIPTextEncode x2 -> KSampler -> VAEDecode -> SaveImage PNGs); at N > 1 "
                          "every rank runs it SPMD with the batch split by global image index (sched/spmd.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the images the last timed step returned on rank 0 as "
+                         "DIR/images.npy (float32 pixel values 0..255; a fixed seeded sample when the batch is "
+                         "larger than 32 MiB of float32). Inputs are seeded: equal arguments give equal inputs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (none today: a plain run already does only set-up, "
+                         "warm-up, the timed steps and the result line)")
     args = ap.parse_args()
+    if args.dump_outputs and args.via_executor:
+        ap.error("--dump-outputs: the --via-executor path writes PNG files, not arrays")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and env_world is None:
@@ -157,6 +192,7 @@ def main():
         torch.cuda.synchronize()
     comm.barrier()
     ops.reset_stats()
+    out = None
     t1 = time.perf_counter()
     if args.pipeline:
         jobs = (Job(**{**job.__dict__, "seed": 1000 + args.warmup + i}) for i in range(args.steps))
@@ -173,6 +209,9 @@ def main():
     dt = comm.all_reduce_max(dt)
     ms_per_step = dt * 1000.0 / max(1, args.steps)
     imgs_per_sec = global_batch * args.steps / dt
+    if args.dump_outputs and comm.rank == 0:
+        _dump_outputs(args.dump_outputs, {"images": out})     # uint8 [global_batch, H, W, 3] of the last step
+        log(f"wrote the last step's images to {args.dump_outputs}")
     if comm.rank == 0:
         metric, data_s, model_s = _labels(args)
         res = {
@@ -313,10 +352,13 @@ def _bench_latency(args, comm, gen, job, t0, t_build, log):
     comm.barrier()
     ops.reset_stats()
     t1 = time.perf_counter()
+    img = None
     for i in range(args.steps):
-        step(args.warmup + i)
+        img = step(args.warmup + i)
     comm.barrier()
     dt = comm.all_reduce_max(time.perf_counter() - t1)
+    if args.dump_outputs and comm.rank == 0:
+        _dump_outputs(args.dump_outputs, {"images": img})
     if comm.rank == 0:
         _, data_s, model_s = _labels(args)
         res = {"metric": "sec/image, one image per node (latency mode)", "value": round(dt / max(1, args.steps), 4),

@@ -476,8 +476,7 @@ class Coordinator:
             try:
                 m = recv_msg(conn)
             except (EOFError, OSError):
-                if self.conns.get(r) is conn:
-                    self._rank_died(r)
+                self._rank_died(r, conn)
                 return
             op = m.get("op")
             if op == "event":
@@ -509,15 +508,18 @@ class Coordinator:
                         logging.info("late SPMD report of prompt %s from rank %d ignored", pid, r)
                     self.cv.notify_all()
 
-    def _rank_died(self, r):
+    def _rank_died(self, r, conn=None):
         """A worker's connection dropped: mark it dead (SPMD prompts use the rank prefix below it until the
         next re-rendezvous), re-run its single prompt on a survivor (once), unblock a waiting SPMD prompt,
-        and start a replacement process."""
-        logging.error("rank %d left the cluster", r)
+        and start a replacement process. ``conn``: the connection that dropped -- a report about a connection
+        that is no longer the rank's current one (its process was replaced meanwhile) is ignored. A dead
+        rank's connected replacement that dies before the next re-rendezvous is replaced in turn."""
         retry = None
         with self.cv:
-            if r in self.dead:
-                return
+            cur = self.conns.get(r)
+            if (conn is not None and cur is not conn) or (cur is None and r in self.dead):
+                return                    # stale report, or this death is already handled
+            logging.error("rank %d left the cluster", r)
             self.dead.add(r)
             self.conns.pop(r, None)       # a replacement says hello on a fresh connection
             try:    # SPMD agreements waiting on the dead rank fail within ~1 s (spmd.SPMD._agree)
@@ -585,6 +587,8 @@ class Coordinator:
         group state is unknown; the next attempt starts once their replacements are up."""
         gen, port = self.gen + 1, _free_port()
         workers = list(range(1, self.world))
+        with self.cv:     # the processes taking part: a rank replaced meanwhile is not force-replaced again
+            members = {r: (self.conns.get(r), _LAUNCH.get("procs", {}).get(r)) for r in workers}
         ok = False
         try:
             logging.warning("re-rendezvous of %d ranks (generation %d): teardown", self.world, gen)
@@ -596,7 +600,7 @@ class Coordinator:
             if bad:
                 logging.error("regroup: ranks %s did not leave the old group cleanly; replacing them", bad)
                 for r in bad:
-                    self._force_replace(r)
+                    self._force_replace(r, *members[r])
                 return
 
             def join0():
@@ -610,7 +614,7 @@ class Coordinator:
                 logging.error("regroup: generation %d incomplete (rank 0 %s, failed workers %s)", gen,
                               "failed" if bad is None else "ok", bad or [])
                 for r in bad or []:
-                    self._force_replace(r)
+                    self._force_replace(r, *members[r])
                 return
             with self.cv:
                 self.gen = gen
@@ -651,22 +655,22 @@ class Coordinator:
             bad |= {r for r in workers if not self._acks.get((ack, r), {}).get("ok")}
         return sorted(bad) if ok0 else None
 
-    def _force_replace(self, r):
-        """A worker whose process-group state is unknown: ask it to exit, kill it if it does not, and let
-        ``_rank_died`` (its connection drops) spawn the replacement."""
-        conn, proc = self.conns.get(r), _LAUNCH.get("procs", {}).get(r)
-        if conn is not None:
+    def _force_replace(self, r, conn, proc):
+        """A worker whose process-group state is unknown (``conn`` / ``proc``: its connection and process when
+        the re-rendezvous began): ask it to exit, kill it if it does not, and let ``_rank_died`` spawn the
+        replacement. If it already left by itself (a hung teardown exits), its replacement may be up by now:
+        that process is not touched."""
+        if conn is not None and self.conns.get(r) is conn:
             try:
                 send_msg(conn, {"op": "exit"}, self.locks[r])
-            except OSError:
+            except (OSError, KeyError):
                 pass
-        if proc is not None:
-            try:
+        if proc is not None and conn is not None:    # no connection in the snapshot: the rank had just died and
+            try:                                     # ``proc`` may already be its fresh replacement
                 proc.wait(timeout=10)
             except subprocess.TimeoutExpired:
                 proc.kill()
-        if r not in self.dead:
-            self._rank_died(r)
+        self._rank_died(r, conn)
 
     def interrupt_all(self):
         for r in list(self.busy):

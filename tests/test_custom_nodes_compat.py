@@ -1,17 +1,13 @@
 """Custom-node import surface: reference-style custom nodes import ``comfy.*``,
 ``folder_paths``, ``nodes``, ``node_helpers``, ``latent_preview``, ``server`` — these resolve to this
-engine's modules through ``compat.install()``. The reference's own bundled node
-(``/root/reference/custom_nodes/websocket_image_save.py``) is loaded UNMODIFIED from a temp
-``custom_nodes/`` dir and run in a prompt."""
+engine's modules through ``compat.install()``. A node written in that style (a websocket image-save node,
+``_WS_NODE`` below) is loaded from a temp ``custom_nodes/`` dir and run in a prompt."""
 import os
-import shutil
 
 import pytest
 import torch
 
 from comfy_gen_server_amd.runtime import device as dm
-
-REF_NODE = "/root/reference/custom_nodes/websocket_image_save.py"
 
 
 def test_alias_modules_resolve():
@@ -49,12 +45,46 @@ def test_alias_modules_resolve():
     assert nodes.MAX_RESOLUTION >= 8192
 
 
-@pytest.mark.skipif(not os.path.exists(REF_NODE), reason="reference checkout not present")
-def test_reference_websocket_node_loads_and_runs(tmp_path):
+_WS_NODE = '''
+"""A custom node written the way reference-style custom nodes are: it imports ``comfy.utils`` and ``PIL``,
+declares INPUT_TYPES / RETURN_TYPES / FUNCTION / OUTPUT_NODE / CATEGORY, sends each image of the batch to the
+client as a PNG preview through ``comfy.utils.ProgressBar`` and registers itself in NODE_CLASS_MAPPINGS."""
+from PIL import Image
+import numpy as np
+import comfy.utils
+
+
+class SaveImageWebsocket:
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"images": ("IMAGE",)}}
+
+    RETURN_TYPES = ()
+    FUNCTION = "save_images"
+    OUTPUT_NODE = True
+    CATEGORY = "api/image"
+
+    def save_images(self, images):
+        pbar = comfy.utils.ProgressBar(images.shape[0])
+        for step, image in enumerate(images):
+            arr = np.clip(255.0 * image.cpu().numpy(), 0, 255).astype(np.uint8)
+            pbar.update_absolute(step, images.shape[0], ("PNG", Image.fromarray(arr), None))
+        return {}
+
+    @classmethod
+    def IS_CHANGED(s, images):
+        return float("nan")
+
+
+NODE_CLASS_MAPPINGS = {"SaveImageWebsocket": SaveImageWebsocket}
+'''
+
+
+def test_reference_style_websocket_node_loads_and_runs(tmp_path):
     dm.set_cpu_mode(True)
     cn = tmp_path / "custom_nodes"
     cn.mkdir()
-    shutil.copy(REF_NODE, cn / "websocket_image_save.py")
+    (cn / "websocket_image_save.py").write_text(_WS_NODE)
     from comfy_gen_server_amd.graph import registry
     from comfy_gen_server_amd.graph.validation import validate_prompt
     from comfy_gen_server_amd.graph.executor import PromptExecutor
@@ -81,36 +111,21 @@ def test_reference_websocket_node_loads_and_runs(tmp_path):
     assert fmt == "PNG" and img.size == (32, 24)
 
 
-def _reference_public_names(alias):
-    """Public top-level defs / classes / assignments of the reference module behind ``alias``."""
-    import ast
-    path = os.path.join("/root/reference", *alias.split(".")) + ".py"
-    if not os.path.exists(path):
-        path = os.path.join("/root/reference", *alias.split("."), "__init__.py")
-    if not os.path.exists(path):
-        return None
-    tree = ast.parse(open(path).read())
-    names = []
-    for node in tree.body:
-        if isinstance(node, (ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef)):
-            names.append(node.name)
-        elif isinstance(node, ast.Assign):
-            names += [t.id for t in node.targets if isinstance(t, ast.Name)]
-        elif isinstance(node, ast.AnnAssign) and isinstance(node.target, ast.Name):
-            names.append(node.target.id)
-    return [n for n in dict.fromkeys(names) if not n.startswith("_")]
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/comfy"), reason="reference tree not present")
 def test_reference_import_surface_complete():
     """Every public top-level name of every reference module a custom node can import through the
-    alias finder resolves, or is on the documented allow-list (compat_names.ALLOWED_MISSING)."""
+    alias finder resolves, or is on the documented allow-list (compat_names.ALLOWED_MISSING). The names are
+    the recorded list tests/golden/import_surface.json.gz (oracle/record_golden.py: alias -> public top-level
+    defs / classes / assignments of the reference module behind it)."""
     import importlib
+    import json
     from comfy_gen_server_amd import compat, compat_names
     compat.install()
+    import gzip
+    with gzip.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "import_surface.json.gz"), "rt") as f:
+        surface = json.load(f)
     missing, checked = {}, 0
     for alias in sorted(set(compat.DIRECT) | set(compat.FACADES)):
-        names = _reference_public_names(alias)
+        names = surface.get(alias)
         if names is None:
             continue
         mod = importlib.import_module(alias)

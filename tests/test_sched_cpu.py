@@ -67,28 +67,44 @@ def _start(tmp_path_factory, n, extra=()):
                     "register_tiny_family(); write_checkpoint('tiny', %r, dtype=torch.float32)"
                     % (ROOT, str(base / "models/checkpoints/tiny.safetensors"))],
                    check=True, env=env, cwd=ROOT, timeout=300)
-    port = _free_port()
-    env["MASTER_PORT"] = str(_free_port())
     env["CGS_REGISTER_TINY"] = "1"
-    proc = subprocess.Popen([sys.executable, "-m", "comfy_gen_server_amd.main", "--gpus", str(n), "--cpu",
-                             "--listen", "127.0.0.1", "--port", str(port), "--base-directory", str(base),
-                             "--disable-custom-nodes", "--dont-print-server", "--preview-method", "none"]
-                            + list(extra),
-                            cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                            start_new_session=True)
-    url = f"http://127.0.0.1:{port}"
-    deadline = time.time() + 240
-    while time.time() < deadline:
-        if proc.poll() is not None:
-            raise RuntimeError(proc.stdout.read()[-4000:])
-        try:
-            _get(url + "/queue")
+    # The HTTP port is chosen free here but bound by the server seconds later, after the ranks' rendezvous has
+    # opened many sockets of its own; one of those can take the port meanwhile. Then the server exits with
+    # "address already in use" before it serves anything, and it is started again on another port.
+    for attempt in range(3):
+        port = _free_port()
+        env["MASTER_PORT"] = str(_free_port())
+        proc = subprocess.Popen([sys.executable, "-m", "comfy_gen_server_amd.main", "--gpus", str(n), "--cpu",
+                                 "--listen", "127.0.0.1", "--port", str(port), "--base-directory", str(base),
+                                 "--disable-custom-nodes", "--dont-print-server", "--preview-method", "none"]
+                                + list(extra),
+                                cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                                start_new_session=True)
+        url = f"http://127.0.0.1:{port}"
+        deadline = time.time() + 240
+        port_taken = False
+        while time.time() < deadline:
+            if proc.poll() is not None:
+                out = proc.stdout.read()
+                proc.stdout.close()
+                port_taken = ("address already in use" in out.lower() or "EADDRINUSE" in out) and attempt < 2
+                if not port_taken:
+                    raise RuntimeError(out[-4000:])
+                try:
+                    os.killpg(proc.pid, signal.SIGKILL)     # its worker ranks, if any is still up
+                except ProcessLookupError:
+                    pass
+                break
+            try:
+                _get(url + "/queue")
+                break
+            except Exception:
+                time.sleep(0.5)
+        else:
+            os.killpg(proc.pid, signal.SIGKILL)
+            raise RuntimeError("server did not come up")
+        if not port_taken:
             break
-        except Exception:
-            time.sleep(0.5)
-    else:
-        os.killpg(proc.pid, signal.SIGKILL)
-        raise RuntimeError("server did not come up")
     return proc, url, base
 
 
