@@ -110,6 +110,8 @@ KERNEL_SIGNATURES = {
     "cgs_timestep_embedding": [_P, _P, _I, _I, _F, _I, _P],
     # elementwise y = silu(x) (bf16)
     "cgs_silu": [_P, _P, _L, _I, _P],
+    # elementwise y = act(x): x, y (may be x), n, CgsAct code, parameter (leaky_relu slope), dtype, stream
+    "cgs_act": [_P, _P, _L, _I, _F, _I, _P],
     # NHWC nearest upsample x2
     "cgs_upsample_nearest2x_nhwc": [_P, _P, _I, _I, _I, _I, _I, _P],
     # depthwise conv NHWC: x, w[k*k, C], bias, y, N, H, W, C, k, replicate, dtype, stream
@@ -146,6 +148,9 @@ KERNEL_SIGNATURES = {
     "cgs_gemm_bf16_w8": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _I, _F, _P],
     "cgs_gemm_bf16_v": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _I, _F, _I, _P],
     "cgs_conv2d_nhwc_v": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    # ... + CgsAct code, parameter: act(conv + bias) (+ res) on the mc::tile kernels (variant 3 / 4 / 8)
+    "cgs_conv2d_nhwc_act": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F,
+                            _P],
     # counter-based noise keyed by (seed, global image index, stream) (csrc/kernels/rng.hip, K18)
     "cgs_philox_randn": [_P, _I, _L, ctypes.c_ulonglong, _L, ctypes.c_ulonglong, _P, _F, _I, _P, _P],
     "cgs_euler_ancestral_philox": [_P, _P, _I, _L, _F, _F, _F, ctypes.c_ulonglong, _L, ctypes.c_ulonglong, _P, _P],

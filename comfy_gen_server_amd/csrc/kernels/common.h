@@ -128,6 +128,74 @@ __device__ __forceinline__ f32x2_t gelu_sig2(f32x2_t x) {
   return x * f32x2_t{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
 }
 
+// The activation set of the fused epilogues and of cgs_act (elementwise.hip). GEMM epilogue flags carry the
+// code in bits 8-10 beside EPI_GELU (code 0 there = erf GELU, the meaning of the flag alone); conv carries it
+// in ConvArgs. The code is a kernel argument, so everything derived from it below is wave-uniform.
+enum CgsAct {
+  CGS_ACT_NONE = 0,
+  CGS_ACT_GELU = 1,         // erf GELU (gelu_sig)
+  CGS_ACT_GELU_TANH = 2,    // x * sigmoid(2 sqrt(2/pi) (x + 0.044715 x^3)) == 0.5 x (1 + tanh(...))
+  CGS_ACT_QUICK_GELU = 3,   // x * sigmoid(1.702 x)
+  CGS_ACT_SILU = 4,
+  CGS_ACT_RELU = 5,
+  CGS_ACT_LEAKY_RELU = 6,   // x >= 0 ? x : p * x
+};
+#define CGS_EPI_ACT_SHIFT 8
+#define CGS_EPI_ACT_MASK (7 << CGS_EPI_ACT_SHIFT)
+__host__ __device__ __forceinline__ int epi_act_code(int epi) { return (epi & CGS_EPI_ACT_MASK) >> CGS_EPI_ACT_SHIFT; }
+
+// The set falls into three branch-free families, so a register-tight epilogue picks the family once (a
+// compile-time path per family) and keeps only two uniform coefficients live:
+//   ACT_FAM_ERF : gelu_sig / gelu_sig2, exactly as the GELU epilogues always ran
+//   ACT_FAM_SIG : x * sigmoid(x * (c0 + c1 x^2)) -- gelu_tanh, quick_gelu, silu: one v_exp_f32 + one
+//                 v_rcp_f32 like gelu_sig; a / b = -c0 * log2(e) / -c1 * log2(e)
+//   ACT_FAM_LIN : x >= 0 ? x : a * x -- relu (a = 0) and leaky_relu (a = slope)
+enum { ACT_FAM_NONE = 0, ACT_FAM_ERF = 1, ACT_FAM_SIG = 2, ACT_FAM_LIN = 3 };
+struct ActFam {
+  int fam;
+  float a, b;
+};
+__device__ __forceinline__ ActFam act_family(int act, float p) {
+  switch (act) {
+    case CGS_ACT_GELU: return ActFam{ACT_FAM_ERF, 0.f, 0.f};
+    case CGS_ACT_GELU_TANH: return ActFam{ACT_FAM_SIG, -2.302208198e+00f, -1.029432396e-01f};
+    case CGS_ACT_QUICK_GELU: return ActFam{ACT_FAM_SIG, -2.455466953e+00f, 0.f};
+    case CGS_ACT_SILU: return ActFam{ACT_FAM_SIG, -1.442695041e+00f, 0.f};
+    case CGS_ACT_RELU: return ActFam{ACT_FAM_LIN, 0.f, 0.f};
+    case CGS_ACT_LEAKY_RELU: return ActFam{ACT_FAM_LIN, p, 0.f};
+    default: return ActFam{ACT_FAM_NONE, 0.f, 0.f};
+  }
+}
+template <int FAM>
+__device__ __forceinline__ float act_fam(float x, float a, float b) {
+  if constexpr (FAM == ACT_FAM_ERF) return gelu_sig(x);
+  else if constexpr (FAM == ACT_FAM_SIG)
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, b, a)));
+  else if constexpr (FAM == ACT_FAM_LIN) return x >= 0.0f ? x : (a != 0.0f ? a * x : 0.0f);   // relu(-inf) = 0
+  else return x;
+}
+template <int FAM>
+__device__ __forceinline__ f32x2_t act_fam2(f32x2_t x, float a, float b) {
+  if constexpr (FAM == ACT_FAM_ERF) return gelu_sig2(x);
+  else if constexpr (FAM == ACT_FAM_SIG) {
+    const f32x2_t t = x * ((x * x) * b + a);
+    const f32x2_t d = f32x2_t{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + 1.0f;
+    return x * f32x2_t{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+  } else return f32x2_t{act_fam<FAM>(x.x, a, b), act_fam<FAM>(x.y, a, b)};
+}
+// One activation of the set on one value (the family chosen by a scalar branch on the uniform code): the
+// sites that are not register-tight -- cgs_act, the skinny GEMM, the fp32 GEMM.
+__device__ __forceinline__ float act_apply(int act, float x, float p) {
+  const ActFam f = act_family(act, p);
+  if (f.fam == ACT_FAM_ERF) return act_fam<ACT_FAM_ERF>(x, f.a, f.b);
+  if (f.fam == ACT_FAM_SIG) return act_fam<ACT_FAM_SIG>(x, f.a, f.b);
+  if (f.fam == ACT_FAM_LIN) return act_fam<ACT_FAM_LIN>(x, f.a, f.b);
+  return x;
+}
+__device__ __forceinline__ f32x2_t act_apply2(int act, f32x2_t x, float p) {
+  return f32x2_t{act_apply(act, x.x, p), act_apply(act, x.y, p)};
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

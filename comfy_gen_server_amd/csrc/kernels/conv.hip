@@ -48,7 +48,20 @@ struct ConvArgs {
   ppk::Split sp;       // v7 split-K tail (S <= 1: none)
   float* gnp;          // v6 only: GroupNorm partial statistics out (pq::run GNS), or null
   int img_rsrc;        // ConvGatherKD: per-image buffer descriptors (an input >= 2 GiB; Ho*Wo % 256 == 0)
+  int act;             // CgsAct code applied to acc + bias before the residual (0: none): the mc::tile kernels
+  float act_param;     //   (variants 3 / 4 / 8) through cgs_conv2d_nhwc_act; act_param = the leaky_relu slope
 };
+
+// The mc::tile epilogue of a conv: bias / residual from the flags, the activation through MC_EPI_GELU + code.
+__device__ __forceinline__ mc::Epi conv_tile_epi(const ConvArgs& a) {
+  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  if (a.act) {
+    e.flags |= MC_EPI_GELU;
+    e.act = a.act;
+    e.act_param = a.act_param;
+  }
+  return e;
+}
 
 // Host: the multiply-shift constants of ConvGatherK (exact for k0 < kh*kw*Cin, kh*kw <= 32).
 static void conv_magic(ConvArgs& a) {
@@ -234,7 +247,9 @@ struct ConvGatherA {
   }
 };
 
-template <int BN, int NW>
+// ACT: the instantiation whose epilogue applies a.act (cgs_conv2d_nhwc_act); the plain one keeps its flags
+// masked to bias / residual, so the activation paths of mc::tile fold away and it compiles as it always did.
+template <int BN, int NW, bool ACT = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4, NW / 4))) void conv_nhwc_v3_kernel(
     ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -246,6 +261,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
   ConvGatherA al;
   al.a = &a;
   mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  if constexpr (ACT) e = conv_tile_epi(a);
   mc::tile<BN, NW>(al, a.w, K, M, a.Cout, K, tm * mc::BM, tn * BN, e, smem);
 }
 
@@ -255,16 +271,20 @@ static void conv_v3_go(ConvArgs& a, hipStream_t stream) {
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)conv_nhwc_v3_kernel<BN, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               mc::Cfg<BN, NW>::LDS);
+    (void)hipFuncSetAttribute((const void*)conv_nhwc_v3_kernel<BN, NW, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, mc::Cfg<BN, NW>::LDS);
     attr = true;
   }
   const int M = a.N * a.Ho * a.Wo;
   a.tiles_n = (a.Cout + BN - 1) / BN;
   const long long nwg = (long long)((M + mc::BM - 1) / mc::BM) * a.tiles_n;
-  conv_nhwc_v3_kernel<BN, NW><<<(unsigned)nwg, 64 * NW, mc::Cfg<BN, NW>::LDS, stream>>>(a);
+  if (a.act) conv_nhwc_v3_kernel<BN, NW, true><<<(unsigned)nwg, 64 * NW, mc::Cfg<BN, NW>::LDS, stream>>>(a);
+  else conv_nhwc_v3_kernel<BN, NW><<<(unsigned)nwg, 64 * NW, mc::Cfg<BN, NW>::LDS, stream>>>(a);
 }
 
 // v8: the v3 main loop on 128 x 128 tiles (two workgroups per CU) for short grids -- the level-2
 // convs at UNet batch 2 (M = 2048) and Cascade's small token grids. Cin % 32 == 0 (v3 gather).
+template <bool ACT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_nhwc_v8_kernel(ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int M = a.N * a.Ho * a.Wo;
@@ -275,6 +295,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   ConvGatherA al;
   al.a = &a;
   mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  if constexpr (ACT) e = conv_tile_epi(a);
   mc::tile<128, 4, ConvGatherA, 128>(al, a.w, K, M, a.Cout, K, tm * 128, tn * 128, e, smem);
 }
 
@@ -282,13 +303,17 @@ static void conv_v8_go(ConvArgs& a, hipStream_t stream) {
   using Cf = mc::Cfg<128, 4, 128>;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS);
+    (void)hipFuncSetAttribute((const void*)conv_nhwc_v8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              Cf::LDS);
+    (void)hipFuncSetAttribute((const void*)conv_nhwc_v8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              Cf::LDS);
     attr = true;
   }
   const int M = a.N * a.Ho * a.Wo;
   a.tiles_n = (a.Cout + 127) / 128;
   const long long nwg = (long long)((M + 127) / 128) * a.tiles_n;
-  conv_nhwc_v8_kernel<<<(unsigned)nwg, 256, Cf::LDS, stream>>>(a);
+  if (a.act) conv_nhwc_v8_kernel<true><<<(unsigned)nwg, 256, Cf::LDS, stream>>>(a);
+  else conv_nhwc_v8_kernel<false><<<(unsigned)nwg, 256, Cf::LDS, stream>>>(a);
 }
 
 // v5: ping-pong schedule (mfma_pp.h), 256 x 256 x 64 tiles; Cin % 64 == 0 (one tap per K-tile).
@@ -1193,6 +1218,24 @@ CGS_EXPORT int cgs_conv2d_nhwc_v(const void* x, const void* x2, int C1, const vo
   ConvArgs a{(const u16*)x, (const u16*)x2, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W,
              Cin, x2 ? C1 : Cin, Cout, kh, kw, stride, pad, Ho, Wo,
              (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0) | (flags & CONV_UP2X), 0, 1};
+  return conv_launch(a, stream, variant);
+}
+
+// cgs_conv2d_nhwc_v with an activation of the set (CgsAct, common.h) on acc + bias, before the residual add:
+// out = act(conv(x) + bias) (+ res). Only the mc::tile kernels carry it: variant 3 / 4 (256-row tiles, 4 / 8
+// waves) or 8 (128 x 128 tiles), Cout % 8 == 0 and Cout > 16; any other variant is refused. act 0 = none.
+CGS_EXPORT int cgs_conv2d_nhwc_act(const void* x, const void* x2, int C1, const void* w, const void* bias,
+                                   const void* res, void* out, int N, int H, int W, int Cin, int Cout, int kh, int kw,
+                                   int stride, int pad, int Ho, int Wo, int flags, int variant, int act,
+                                   float act_param, hipStream_t stream) {
+  if (Cin % 32 || (x2 && (C1 % 32)) || Cout <= 16 || Cout % 8 || (variant != 3 && variant != 4 && variant != 8) ||
+      act < CGS_ACT_NONE || act > CGS_ACT_LEAKY_RELU)
+    return (int)hipErrorInvalidValue;
+  ConvArgs a{(const u16*)x, (const u16*)x2, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W,
+             Cin, x2 ? C1 : Cin, Cout, kh, kw, stride, pad, Ho, Wo,
+             (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0) | (flags & CONV_UP2X), 0, 1};
+  a.act = act;
+  a.act_param = act_param;
   return conv_launch(a, stream, variant);
 }
 

@@ -1,6 +1,7 @@
 // Small fused element-wise kernels of the sampling loop and the UNet (K12, K13, K16, K08-standalone).
 // All memory-bound: 16-byte vectors, grid-stride loops capped at 8192 blocks.
 #include "common.h"
+#include <type_traits>
 
 static inline int ew_blocks(long long n_vec) {
   long long b = (n_vec + 255) / 256;
@@ -29,6 +30,85 @@ CGS_EXPORT int cgs_silu(const void* x, void* y, long long n, int dtype, hipStrea
   else if (dtype == CGS_F16) silu_kernel<CGS_F16><<<blocks, 256, 0, stream>>>((const u16*)x, (u16*)y, n);
   else return (int)hipErrorInvalidValue;
   return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- activation set (CgsAct), y == x allowed
+// 16-B vectors (8 x bf16 / fp16, 4 x fp32) + a scalar tail; four independent vectors in flight per thread
+// (the loads of one round are issued before any of its stores: deeper memory-level parallelism on the
+// full-resolution image tensors), each block on its own 16 KiB run of the tensor. One instantiation per activation family (common.h), so the loop body is
+// branch-free. fp32 data takes the exact erf for GELU (the sigmoid form's 2.6e-5 is below a bf16 ulp, not
+// below an fp32 one).
+template <int DT, int FAM>
+__device__ __forceinline__ float act_elem(float v, float a, float b) {
+  if constexpr (DT == CGS_F32 && FAM == ACT_FAM_ERF) return gelu_f(v);
+  else return act_fam<FAM>(v, a, b);
+}
+
+template <int DT, int FAM>
+__global__ __launch_bounds__(256) void act_kernel(const void* xv, void* yv, long long n, float a, float b) {
+  constexpr int U = 4;                                     // vectors in flight per thread
+  constexpr int VE = DT == CGS_F32 ? 4 : 8;                // elements per 16-B vector
+  typedef typename std::conditional<DT == CGS_F32, float4_t, s16x8>::type vec_t;
+  const long long gtid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  const long long gstride = (long long)gridDim.x * blockDim.x;
+  const long long nv = n / VE;
+  const vec_t* xp = reinterpret_cast<const vec_t*>(xv);
+  vec_t* yp = reinterpret_cast<vec_t*>(yv);
+  auto apply = [&](vec_t v) {
+    vec_t o;
+#pragma unroll
+    for (int j = 0; j < VE; ++j) {
+      if constexpr (DT == CGS_F32) o[j] = act_elem<DT, FAM>(v[j], a, b);
+      else o[j] = (short)cvt_out<DT>(act_elem<DT, FAM>(cvt_in<DT>((u16)v[j]), a, b));
+    }
+    return o;
+  };
+  // full rounds: a block owns U * 256 consecutive vectors (16 KiB), a thread every 256th of them
+  const long long rounds = nv / (U * 256);
+  for (long long r = blockIdx.x; r < rounds; r += gridDim.x) {
+    const long long i = r * (U * 256) + threadIdx.x;
+    vec_t v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = xp[i + u * 256];
+#pragma unroll
+    for (int u = 0; u < U; ++u) yp[i + u * 256] = apply(v[u]);
+  }
+  for (long long i = rounds * (U * 256) + gtid; i < nv; i += gstride) yp[i] = apply(xp[i]);
+  const long long t = nv * VE + gtid;
+  if (t < n) {
+    if constexpr (DT == CGS_F32) ((float*)yv)[t] = act_elem<DT, FAM>(((const float*)xv)[t], a, b);
+    else ((u16*)yv)[t] = cvt_out<DT>(act_elem<DT, FAM>(cvt_in<DT>(((const u16*)xv)[t]), a, b));
+  }
+}
+
+template <int DT>
+static int act_launch(const void* x, void* y, long long n, int act, float param, hipStream_t stream) {
+  float a = 0.f, b = 0.f;      // the family coefficients of act_family (common.h)
+  int fam;
+  switch (act) {
+    case CGS_ACT_GELU: fam = ACT_FAM_ERF; break;
+    case CGS_ACT_GELU_TANH: fam = ACT_FAM_SIG; a = -2.302208198e+00f; b = -1.029432396e-01f; break;
+    case CGS_ACT_QUICK_GELU: fam = ACT_FAM_SIG; a = -2.455466953e+00f; break;
+    case CGS_ACT_SILU: fam = ACT_FAM_SIG; a = -1.442695041e+00f; break;
+    case CGS_ACT_RELU: fam = ACT_FAM_LIN; break;
+    case CGS_ACT_LEAKY_RELU: fam = ACT_FAM_LIN; a = param; break;
+    default: return (int)hipErrorInvalidValue;
+  }
+  // 4 vectors per thread per round: a quarter of the one-vector-per-thread grid
+  const int blocks = ew_blocks(n / ((DT == CGS_F32 ? 4 : 8) * 4) + 1);
+  if (fam == ACT_FAM_ERF) act_kernel<DT, ACT_FAM_ERF><<<blocks, 256, 0, stream>>>(x, y, n, a, b);
+  else if (fam == ACT_FAM_SIG) act_kernel<DT, ACT_FAM_SIG><<<blocks, 256, 0, stream>>>(x, y, n, a, b);
+  else act_kernel<DT, ACT_FAM_LIN><<<blocks, 256, 0, stream>>>(x, y, n, a, b);
+  return (int)hipGetLastError();
+}
+
+CGS_EXPORT int cgs_act(const void* x, void* y, long long n, int act, float param, int dtype, hipStream_t stream) {
+  if (n < 0 || (((uintptr_t)x | (uintptr_t)y) % 16)) return (int)hipErrorInvalidValue;
+  if (n == 0) return act >= CGS_ACT_GELU && act <= CGS_ACT_LEAKY_RELU ? 0 : (int)hipErrorInvalidValue;
+  if (dtype == CGS_BF16) return act_launch<CGS_BF16>(x, y, n, act, param, stream);
+  if (dtype == CGS_F16) return act_launch<CGS_F16>(x, y, n, act, param, stream);
+  if (dtype == CGS_F32) return act_launch<CGS_F32>(x, y, n, act, param, stream);
+  return (int)hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------- CFG combine (fp32)

@@ -203,7 +203,10 @@ __global__ __launch_bounds__(256) void f32_gemm_kernel(const F32Gemm g) {
         const int m = m0 + wm + 16 * i + (lane >> 4) * 4 + r;
         if (m >= g.M) continue;
         float v = __builtin_fmaf(acc[i][j][r], g.alpha, bv);
-        if (g.epi & F_GELU) v = gelu_f(v);
+        if (g.epi & F_GELU) {   // alone: the exact erf GELU; with a CgsAct code in bits 8-10: that activation
+          if (epi_act_code(g.epi) <= CGS_ACT_GELU) v = gelu_f(v);
+          else v = act_apply(epi_act_code(g.epi), v, 0.f);
+        }
         if (g.epi & F_RES) v += g.R[(long long)m * g.ldr + n];
         Cb[(long long)m * g.ldc + n] = v;
       }
@@ -236,6 +239,7 @@ CGS_EXPORT int cgs_gemm_f32(const float* A, const float* B, float* C, const floa
   if (K <= 0 || lda % 4 || ldb % 4 || sab % 4 || sbb % 4 || !al16(A) || !al16(B) || (bkn && N % 4))
     return (int)hipErrorInvalidValue;
   if (((epi & F_BIAS) && !bias) || ((epi & F_RES) && !R)) return (int)hipErrorInvalidValue;
+  if ((epi & CGS_EPI_ACT_MASK) && (!(epi & F_GELU) || epi_act_code(epi) > CGS_ACT_RELU)) return (int)hipErrorInvalidValue;
   F32Gemm g{};
   g.A = A; g.B = B; g.C = C; g.bias = bias; g.R = R;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr; g.sab = sab; g.sbb = sbb; g.scb = scb;

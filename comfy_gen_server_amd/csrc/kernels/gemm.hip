@@ -27,6 +27,8 @@
 #define EPI_LNFOLD 8
 #define EPI_F32OUT 16   // fp32 C (v7 only; attention scores of the wide-head path)
 #define EPI_GELU 32     // GELU(acc * alpha + bias) before the residual: v6 (ACT kernel), mc::tile kernels, skinny
+// EPI_GELU | (CgsAct code << 8): that activation of the set (common.h) instead of the erf GELU -- the same
+// kernels through cgs_gemm_bf16 / _v only; every other entry point refuses the code bits (CGS_EPI_ACT_MASK)
 
 // fp8 e4m3fn (OCP) -> bf16 bits, exact (every e4m3 value is a bf16 value); NaN stays NaN.
 __device__ __forceinline__ u16 fp8e4m3_to_bf16(uint32_t b) {
@@ -390,6 +392,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
   grouped_tile(logical, gridDim.x / tiles_n, tiles_n, group_m, tm, tn);
   DenseA al{A, lda, M, {}};
   mc::Epi e{C, bias, R, ldc, ldr, epi, alpha};
+  e.act = epi_act_code(epi);
   mc::tile<BN, NW>(al, W, ldw, M, N, K, tm * mc::BM, tn * BN, e, smem);
 }
 
@@ -408,6 +411,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   grouped_tile(logical, gridDim.x / tiles_n, tiles_n, group_m, tm, tn);
   DenseA al{A, lda, M, {}};
   mc::Epi e{C, bias, R, ldc, ldr, epi, alpha, rs, cs};
+  e.act = epi_act_code(epi);
   mc::tile<BN, 4, DenseA, BMV, NS>(al, W, ldw, M, N, K, tm * BMV, tn * BN, e, smem);
 }
 
@@ -691,7 +695,7 @@ struct DenseKB {
 // ------------------------------------------------------------------------------------------------
 // v6: 256 x 160 x 64 ping-pong (mfma_pp160.h): whole-round tile counts on the SDXL channel widths.
 // NI: 16-row MFMA blocks per wave -- 4 (256 x 160 tiles) or 2 (128 x 160: variant 19, the short-M grids)
-template <bool LN = false, int DS = 0, bool GG = false, bool ACT = false, bool RSO = false, int NI = 4>
+template <bool LN = false, int DS = 0, bool GG = false, int ACT = 0, bool RSO = false, int NI = 4>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_bf16_nt_v6_kernel(
     const u16* __restrict__ A, const u16* __restrict__ W, u16* __restrict__ C, const u16* __restrict__ bias,
     const u16* __restrict__ R, int M, int N, int K, long long lda, long long ldw, long long ldc, long long ldr,
@@ -702,6 +706,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // (profiles/r03/v6_offsets32.log)
   mc::Epi e{C, bias, R, ldc, ldr, epi, alpha, rs, cs};
   e.gnp = rso;    // RSO: per-row LayerNorm statistics partials out
+  if constexpr (ACT > 1) e.act = epi_act_code(epi);
   if constexpr ((DS & 64) != 0) {
     DenseKB al;
     al.A = A;
@@ -757,7 +762,7 @@ int v6_conv_ds() {
 }
 CGS_EXPORT void cgs_v6_set_mode(int m) { g_v6_ds = m; g_v6_conv_ds = m; }
 
-template <bool LN, int DS, bool GG = false, bool ACT = false, bool RSO = false, int NI = 4>
+template <bool LN, int DS, bool GG = false, int ACT = 0, bool RSO = false, int NI = 4>
 static void gemm_v6_go(int grid, const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
                        int K, long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
                        int tiles_m, int tiles_n, hipStream_t stream, const float* rs, const float* cs,
@@ -825,6 +830,16 @@ static int gemm_v6_launch(const void* A, const void* W, void* C, const void* bia
   if ((long long)N * ldw * 2 >= (1ll << 31)) ds &= ~128;
   if (epi & EPI_GELU) {    // GELU epilogue: plain or LayerNorm-folded form (no GEGLU)
     if (epi & EPI_GEGLU) return (int)hipErrorInvalidValue;
+    if (epi_act_code(epi) > CGS_ACT_GELU) {   // another activation of the set: its family's kernel, no LN fold
+      if (epi & EPI_LNFOLD) return (int)hipErrorInvalidValue;
+      if (epi_act_code(epi) >= CGS_ACT_RELU)
+        gemm_v6_go<false, 1, false, ACT_FAM_LIN>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
+                                                 tiles_m, tiles_n, stream, rs, cs);
+      else
+        gemm_v6_go<false, 1, false, ACT_FAM_SIG>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
+                                                 tiles_m, tiles_n, stream, rs, cs);
+      return (int)hipGetLastError();
+    }
     if (epi & EPI_LNFOLD)
       gemm_v6_go<true, 1, false, true>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m,
                                        tiles_n, stream, rs, cs);
@@ -1123,7 +1138,10 @@ __global__ __launch_bounds__(64 * SK_WAVES) void gemm_skinny_kernel(const u16* _
       const int row = mr * 16 + fq * 4 + r;
       if (row < M && col < N) {
         float o = v[r] * alpha + bv;
-        if (epi & EPI_GELU) o = gelu_sig(o);
+        if (epi & EPI_GELU) {
+          if (epi_act_code(epi) <= CGS_ACT_GELU) o = gelu_sig(o);
+          else o = act_apply(epi_act_code(epi), o, 0.f);
+        }
         if (epi & EPI_RESIDUAL) o += bf2f(R[(long long)row * ldr + col]);
         C[(long long)row * ldc + col] = f2bf(o);
       }
@@ -1199,7 +1217,7 @@ CGS_EXPORT int cgs_gemm_skinny_ws(const void* A, const void* W, void* C, const v
                                   int K, long long lda, long long ldw, long long ldc, long long ldr, int epi,
                                   float alpha, void* ws, long long ws_bytes, hipStream_t stream) {
   if (M > 128 || K % 32 || lda % 8 || ldw % 8 || (((uintptr_t)A | (uintptr_t)W) % 16) ||
-      (epi & (EPI_GEGLU | EPI_F32OUT | EPI_LNFOLD)))
+      (epi & (EPI_GEGLU | EPI_F32OUT | EPI_LNFOLD | CGS_EPI_ACT_MASK)))   // (the split reduce knows the erf GELU only)
     return (int)hipErrorInvalidValue;
   if (M == 0 || N == 0) return 0;
   return gemm_skinny_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, ws, ws_bytes);
@@ -1230,10 +1248,13 @@ static int gemm_dispatch(const void* A, const void* W, void* C, const void* bias
                          int variant, hipStream_t stream, void* ws = nullptr, long long ws_bytes = 0) {
   if (K % 8 || lda % 8 || ldw % 8) return (int)hipErrorInvalidValue;
   if ((epi & EPI_GEGLU) && (N % 32)) return (int)hipErrorInvalidValue;
+  // activation code bits: only beside EPI_GELU, only the codes a GEMM knows (leaky_relu has no parameter here)
+  if ((epi & CGS_EPI_ACT_MASK) && (!(epi & EPI_GELU) || epi_act_code(epi) > CGS_ACT_RELU)) return (int)hipErrorInvalidValue;
   if (M == 0 || N == 0) return 0;
   if (epi & EPI_GELU) {
-    // GELU epilogue kernels: skinny (M <= 128), v6 (variant 6), the mc::tile family (v3 / v4, v8 and the
-    // small tiles; auto = v8). No GEGLU / LayerNorm-fold / fp32-out combination.
+    // GELU (or EPI_GELU | code << 8: another activation) epilogue kernels: skinny (M <= 128), v6 (variant 6),
+    // the mc::tile family (v3 / v4, v8 and the small tiles; auto = v8). No GEGLU / LayerNorm-fold / fp32-out
+    // combination.
     if (epi & (EPI_GEGLU | EPI_LNFOLD | EPI_F32OUT)) return (int)hipErrorInvalidValue;
     const bool ok = (K % 32 == 0) && (N % 8 == 0) && (ldc % 8 == 0) && (!(epi & EPI_RESIDUAL) || ldr % 8 == 0) &&
                     ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)R)) % 16 == 0);
@@ -1317,7 +1338,8 @@ static int gemm_dispatch(const void* A, const void* W, void* C, const void* bias
 CGS_EXPORT int cgs_gemm_bf16_w8(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
                                 int K, long long lda, long long ldw, long long ldc, long long ldr, int epi,
                                 float alpha, hipStream_t stream) {
-  if (K % 8 || lda % 8 || ldw % 8 || ((uintptr_t)W & 7) || ((uintptr_t)A & 15)) return (int)hipErrorInvalidValue;
+  if (K % 8 || lda % 8 || ldw % 8 || ((uintptr_t)W & 7) || ((uintptr_t)A & 15) || (epi & CGS_EPI_ACT_MASK))
+    return (int)hipErrorInvalidValue;
   if ((epi & EPI_GEGLU) && (N % 32)) return (int)hipErrorInvalidValue;
   if (M == 0 || N == 0) return 0;
   const int tiles_m = (M + G_BM - 1) / G_BM, tiles_n = (N + G_BN - 1) / G_BN;
@@ -1354,6 +1376,7 @@ static int gemm_lnfold(const void* A, const void* W, void* C, const void* bias, 
                        int M, int N, int K, long long lda, long long ldw, long long ldc, int epi, void* ws,
                        long long ws_bytes, int variant, hipStream_t stream) {
   const int nout = (epi & EPI_GEGLU) ? N / 2 : N;
+  if (epi & CGS_EPI_ACT_MASK) return (int)hipErrorInvalidValue;   // LN-folded forms: erf GELU only
   if (!rs || !cs || K % 64 || K < 128 || lda % 8 || ldw % 8 || ldc % 8 || nout % 8 || (epi & EPI_RESIDUAL) ||
       ((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 || ((uintptr_t)bias % 8) || ((uintptr_t)cs % 16) ||
       ((uintptr_t)rs % 8) || (long long)M * lda * 2 >= (1ll << 32) || (long long)N * ldw * 2 >= (1ll << 32))

@@ -537,7 +537,7 @@ CGS_EXPORT int cgs_gemm_w6_ok(int M, int N, int K, long long lda, long long ldw,
   const bool gg = (epi & MC_EPI_GEGLU) != 0;
   if (bn != 256 && bn != 160) return 0;
   if (K % 128 || K < 128 || N % 16 || lda % 8 || ldw % 8 || ldc % 8 || ((epi & MC_EPI_RESIDUAL) && ldr % 8)) return 0;
-  if (epi & (MC_EPI_F32OUT | MC_EPI_GELU)) return 0;
+  if (epi & (MC_EPI_F32OUT | MC_EPI_GELU | CGS_EPI_ACT_MASK)) return 0;   // no activation epilogue of any kind
   if (gg && ((epi & MC_EPI_RESIDUAL) || N % 32 || bn != 256)) return 0;
   if ((epi & MC_EPI_LNFOLD) && (epi & MC_EPI_RESIDUAL)) return 0;
   if ((long long)M * lda * 2 >= (1ll << 31) || (long long)N * ldw * 2 >= (1ll << 31)) return 0;

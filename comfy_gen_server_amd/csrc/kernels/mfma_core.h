@@ -83,6 +83,8 @@ struct Epi {
   const float* cs = nullptr;   // MC_EPI_LNFOLD: per-column sums of the gamma-scaled weight rows
   float* gnp = nullptr;        // GroupNorm statistics out (pq::run GNS): per-(image, 64-row block, column)
   int hw = 0;                  //   (mean, M2) partials in the gn_partial layout; hw = rows per image
+  int act = 0;                 // MC_EPI_GELU: the CgsAct code applied instead of the erf GELU (0 / CGS_ACT_GELU: erf)
+  float act_param = 0.f;       //   its parameter (the leaky_relu slope)
 };
 
 // s_waitcnt with only vmcnt constrained (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14])
@@ -290,9 +292,11 @@ __device__ __forceinline__ void tile(AL& al, const u16* __restrict__ W, long lon
       });
     });
   } else {
-    // plain / GELU (MC_EPI_GELU) forms as two straight-line paths: the flag is wave-uniform
+    // plain / GELU (MC_EPI_GELU) / other activation (MC_EPI_GELU + e.act) forms as straight-line paths: the
+    // flag and the code are wave-uniform
+    const ActFam af = act_family(e.act, e.act_param);   // (e.act 0 / CGS_ACT_GELU: the erf path below)
     auto plain = [&](auto act_c) {
-      constexpr bool ACT = decltype(act_c)::value;
+      constexpr int ACT = decltype(act_c)::value;
 #pragma unroll
       for (int j = 0; j < C::NJ; ++j) {
         const int oc = 32 * j + ecol;
@@ -311,15 +315,18 @@ __device__ __forceinline__ void tile(AL& al, const u16* __restrict__ W, long lon
               v = st.y * (t[r] - st.x * csl);
             }
             v += bv;
-            if constexpr (ACT) v = gelu_sig(v);
+            if constexpr (ACT == ACT_FAM_ERF) v = gelu_sig(v);
+            else if constexpr (ACT != ACT_FAM_NONE) v = act_fam<ACT>(v, af.a, af.b);
             *reinterpret_cast<u16*>(region + row * pitch + 16 * ((oc >> 3) ^ (row & (CPR - 1))) + 2 * (oc & 7)) =
                 f2bf(v);
           }
         }
       }
     };
-    if (e.flags & MC_EPI_GELU) plain(std::true_type{});
-    else plain(std::false_type{});
+    if (!(e.flags & MC_EPI_GELU)) plain(std::integral_constant<int, ACT_FAM_NONE>{});
+    else if (af.fam == ACT_FAM_SIG) plain(std::integral_constant<int, ACT_FAM_SIG>{});
+    else if (af.fam == ACT_FAM_LIN) plain(std::integral_constant<int, ACT_FAM_LIN>{});
+    else plain(std::integral_constant<int, ACT_FAM_ERF>{});
   }
   // wave-local region: only this wave's LDS writes must land before its reads (lgkmcnt wait is
   // inserted by the compiler); then 16-B row-wise reads -> (+ residual) -> 16-B global stores.

@@ -107,6 +107,7 @@ __device__ __forceinline__ int gg_row160(int r) {
 // rows = 5 interleave groups = 80 output columns per tile (whole rounds where the 256-wide tiles leave a
 // partial one, e.g. SDXL batch 1: M = 2048, N = 10240 -> 512 tiles vs 320). Host: N % 160 == 0.
 // ACT: GELU on (acc * alpha + bias) before the residual add (MC_EPI_GELU: Cascade's ChannelMLP Linear -> GELU).
+//   ACT = 1 (true) is that erf GELU; ACT = ACT_FAM_SIG / ACT_FAM_LIN apply e.act's family (common.h) instead.
 // RSO: the epilogue also writes per-row LayerNorm statistics partials of the stored (bf16) outputs -- per row
 // and 80-column chunk (one wave's columns), (mean, M2) shifted by the row's first value in the chunk -- into
 // e.gnp as [M][N / 80][2] floats; a LayerNorm over these rows then needs only cgs_ln_rs_from_partials
@@ -114,7 +115,7 @@ __device__ __forceinline__ int gg_row160(int r) {
 // PFE: epilogue operands (bias, LayerNorm-fold statistics, residual) prefetched one K-tile ahead -- see
 // `prefetch` -- with the last two K-tiles peeled (1), or only bias / LN statistics, inside the K loop (2: the
 // conv gathers, whose peeled loop and whose prefetched residual spilled), or loaded in the epilogue (0).
-template <class AL, bool LN = false, int DS = 0, int GNS = 0, bool GG = false, bool ACT = false,
+template <class AL, bool LN = false, int DS = 0, int GNS = 0, bool GG = false, int ACT = 0,
           bool RSO = false, int PFE = 1, int NJ = 5, int NI = 4, int NW = 8>
 __device__ __forceinline__ void run(AL& al, const u16* __restrict__ W, long long ldw, int M, int N, int K,
                                     const mc::Epi& e, unsigned char* smem, int tiles_m, int tiles_n, int group_m) {
@@ -368,11 +369,15 @@ __device__ __forceinline__ void run(AL& al, const u16* __restrict__ W, long long
         if constexpr (NJ == 5) rw[i][4] = uint2{prw2[i].x, prw2[i].y};
       }
     }
+    const ActFam af = act_family(e.act, e.act_param);
     auto val = [&](int i, int j) {
       float v0 = acc[i][j][0] * e.alpha + bv[j].x, v1 = acc[i][j][1] * e.alpha + bv[j].y;
       float v2 = acc[i][j][2] * e.alpha + bv[j].z, v3 = acc[i][j][3] * e.alpha + bv[j].w;
-      if constexpr (ACT) {
+      if constexpr (ACT == 1) {
         const f32x2_t g01 = gelu_sig2(f32x2_t{v0, v1}), g23 = gelu_sig2(f32x2_t{v2, v3});
+        v0 = g01.x; v1 = g01.y; v2 = g23.x; v3 = g23.y;
+      } else if constexpr (ACT != 0) {
+        const f32x2_t g01 = act_fam2<ACT>(f32x2_t{v0, v1}, af.a, af.b), g23 = act_fam2<ACT>(f32x2_t{v2, v3}, af.a, af.b);
         v0 = g01.x; v1 = g01.y; v2 = g23.x; v3 = g23.y;
       }
       if (HR) {

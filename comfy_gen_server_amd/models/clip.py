@@ -6,8 +6,9 @@ argmax token, text_projection; CLIPVisionModelProjection). Internal keys follow 
 transformers layout (``text_model.encoder.layers.N.self_attn.q_proj`` ...); OpenCLIP checkpoints
 (SD2 / SDXL-G / Cascade) are converted at load time by ``runtime/convert.py``.
 
-Device path: q/k/v one fused GEMM, causal flash attention kernel, residual adds fused into the
-out_proj / fc2 GEMM epilogues. Latency-bound (M = 77 x prompts) — batch every prompt of a job
+Device path: q/k/v one fused GEMM, causal flash attention kernel, the MLP activation (quick_gelu / gelu /
+gelu_pytorch_tanh) fused into the fc1 GEMM epilogue, residual adds fused into the out_proj / fc2 GEMM
+epilogues. Latency-bound (M = 77 x prompts) — batch every prompt of a job
 into one call.
 """
 from __future__ import annotations
@@ -19,6 +20,7 @@ from .. import ops
 from .layers import DerivedMixin, Embedding, LayerNorm, Linear, Conv2d
 
 
+# the activations' definitions (``ops.linear(act=...)`` applies the same expressions on the CPU path)
 ACTS = {
     "quick_gelu": lambda x: x * torch.sigmoid(1.702 * x),
     "gelu": lambda x: torch.nn.functional.gelu(x),
@@ -53,11 +55,12 @@ class CLIPMLP(nn.Module):
     def __init__(self, embed_dim, intermediate, activation, dtype=None, device=None):
         super().__init__()
         self.fc1 = Linear(embed_dim, intermediate, True, dtype=dtype, device=device)
-        self.act = ACTS[activation]
+        assert activation in ACTS, activation
+        self.act = activation
         self.fc2 = Linear(intermediate, embed_dim, True, dtype=dtype, device=device)
 
     def forward(self, x, residual=None):
-        return self.fc2(self.act(self.fc1(x)), residual=residual)
+        return self.fc2(self.fc1(x, act=self.act), residual=residual)
 
 
 class CLIPLayer(nn.Module):

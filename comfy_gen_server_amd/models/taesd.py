@@ -3,7 +3,8 @@
 Used for live previews (runtime.preview) and as the virtual ``taesd`` / ``taesdxl`` VAEs. All convs
 are 64-wide 3x3 — on the device they take the NHWC implicit-GEMM conv kernel, and each
 "nearest 2x upsample + conv" pair of the decoder is one fused kernel (the input is read through the
-upsample, the 4x tensor is never written). Key names match the released checkpoints
+upsample, the 4x tensor is never written). The ReLU after a conv is that conv's epilogue (``act="relu"``);
+a Block's final ReLU comes after the skip add, so it is the native in-place activation. Key names match the released checkpoints
 (``taesd_encoder.N.*`` / ``taesd_decoder.N.*``).
 """
 from __future__ import annotations
@@ -33,10 +34,11 @@ class Block(nn.Module):
 
     def forward(self, x):
         c = self.conv
-        h = torch.relu(c[0](x))
-        h = torch.relu(c[2](h))
+        h = c[0](x, act="relu")
+        h = c[2](h, act="relu")
         skip = x if isinstance(self.skip, nn.Identity) else self.skip(x)
-        return torch.relu(c[4](h, residual=skip))      # residual add fused into the last conv
+        # residual add fused into the last conv; the ReLU follows the add, so it is not an epilogue
+        return ops.activation(c[4](h, residual=skip), "relu", inplace=True)
 
 
 class Upsample2x(nn.Module):
@@ -69,14 +71,16 @@ def _run(seq, x):
     i = 0
     while i < len(mods):
         m = mods[i]
-        if isinstance(m, Upsample2x) and i + 1 < len(mods) and isinstance(mods[i + 1], Conv2d):
-            x = mods[i + 1](x, upsample2x=True)
-            i += 2
+        up = isinstance(m, Upsample2x) and i + 1 < len(mods) and isinstance(mods[i + 1], Conv2d)
+        if up:
+            i += 1
+            m = mods[i]
+        if isinstance(m, Conv2d):      # (+ the upsample in front, + the ReLU behind: one kernel)
+            relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            x = m(x, upsample2x=up, act="relu" if relu else None)
+            i += 2 if relu else 1
             continue
-        if isinstance(m, nn.ReLU):
-            x = torch.relu(x)
-        else:
-            x = m(x)
+        x = ops.activation(x, "relu") if isinstance(m, nn.ReLU) else m(x)
         i += 1
     return x
 

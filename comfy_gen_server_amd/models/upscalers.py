@@ -26,8 +26,9 @@ class UnsupportedModel(Exception):
     pass
 
 
-def _lrelu(x):
-    return F.leaky_relu(x, 0.2)
+def _conv_lrelu(conv, x, **kw):
+    """conv -> LeakyReLU(0.2) as one op: the activation is the conv's epilogue (``ops.conv2d(act=...)``)."""
+    return conv(x, act="leaky_relu", act_param=0.2, **kw)
 
 
 class ResidualDenseBlock5C(nn.Module):
@@ -41,7 +42,7 @@ class ResidualDenseBlock5C(nn.Module):
     def forward(self, x):
         feats = [x]
         for i in range(4):
-            feats.append(_lrelu(getattr(self, f"conv{i + 1}")[0](torch.cat(feats, 1) if len(feats) > 1 else x)))
+            feats.append(_conv_lrelu(getattr(self, f"conv{i + 1}")[0], torch.cat(feats, 1) if len(feats) > 1 else x))
         return self.conv5[0](torch.cat(feats, 1)) * 0.2 + x
 
 
@@ -161,8 +162,8 @@ class RRDBNet(nn.Module):
         h = m["0"](x)
         h = m["1"](h)
         for name in self._ups:       # nearest x2 + conv: one fused kernel on the device
-            h = _lrelu(m[name](h, upsample2x=True))
-        h = m[self._last](_lrelu(m[self._hr](h)))
+            h = _conv_lrelu(m[name], h, upsample2x=True)
+        h = m[self._last](_conv_lrelu(m[self._hr], h))
         if self.shuffle_factor:
             h = h[:, :, : h_in * self.scale, : w_in * self.scale]
         return h
@@ -288,8 +289,8 @@ class SPSRNet(nn.Module):
             feats.append(y)
         y = trunk[-1](y, residual=h)               # LR conv + long skip
         for name in self._ups:
-            y = _lrelu(m[name](y, upsample2x=True))
-        y = _lrelu(self.HR_conv0_new[0](y))
+            y = _conv_lrelu(m[name], y, upsample2x=True)
+        y = _conv_lrelu(self.HR_conv0_new[0], y)
         y = self.HR_conv1_new[0](y)
         b_fea = self.b_fea_conv[0](g)
         xb = b_fea
@@ -298,7 +299,7 @@ class SPSRNet(nn.Module):
         xb = self.b_LR_conv[0](xb, residual=b_fea)
         xb = self.b_module(xb)
         f = self.f_concat[0](self.f_block(torch.cat([xb, y], 1)))
-        return self.f_HR_conv1[0](_lrelu(self.f_HR_conv0[0](f)))
+        return self.f_HR_conv1[0](_conv_lrelu(self.f_HR_conv0[0], f))
 
 
 class _SepConv(nn.Module):

@@ -26,7 +26,8 @@ EPI_RESIDUAL = 2
 EPI_GEGLU = 4
 EPI_SILU_IN = 8   # reserved
 EPI_LNFOLD = 8    # (C side: MC_EPI_LNFOLD; the LN-folded entry points add it themselves)
-EPI_GELU = 32     # GELU(acc + bias) before the residual (v6 ACT kernel, mc::tile family, skinny)
+EPI_GELU = 32     # GELU(acc + bias) before the residual (v6 ACT kernel, mc::tile family, skinny); with a
+#                   CgsAct code in bits 8-10 (``ACT_CODES[name] << 8``) that activation instead of the erf GELU
 
 # hipBLASLt (through ATen) as a GEMM autotune candidate: off unless explicitly requested -- the
 # hand-written MFMA kernels (v5/v6/v7) are the device GEMMs; profiles/r02_gemm_table_v7.md has the
@@ -94,7 +95,9 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
            residual: torch.Tensor | None = None, act: str | None = None,
            out: torch.Tensor | None = None, row_stats: bool = False) -> torch.Tensor:
     """y = act(x @ weight^T (+ bias)) (+ residual). ``residual`` has y's shape (fused epilogue add);
-    ``act="gelu"`` fuses the GELU into the epilogue (Cascade ChannelMLP Linear -> GELU); ``out``: a
+    ``act="gelu"`` fuses the GELU into the epilogue (Cascade ChannelMLP Linear -> GELU), and so do
+    ``"gelu_tanh"`` (alias ``"gelu_pytorch_tanh"``), ``"quick_gelu"``, ``"silu"`` and ``"relu"`` (the CLIP
+    MLPs) on the kernels whose epilogue carries the activation code (v6, v4, v8, small tiles, skinny); ``out``: a
     contiguous [rows, N] destination for the device path (e.g. one image's slice of a batch).
     ``row_stats``: when the shape runs on the v6 kernel, its epilogue also writes per-row LayerNorm
     statistics partials of y, attached as ``y._cgs_rowpart`` (see ``layernorm_stats_for``) -- the next
@@ -103,7 +106,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
     Device path: the HIP GEMM family (v7 persistent ping-pong 256x256x64 with a register epilogue,
     v6 persistent 256x160, v5 ping-pong 256x256, v3 8-wave 32x32 MFMA, v1 128x128), the kernel picked
     per shape by ``ops.autotune`` (hipBLASLt joins the candidates only with ``CGS_GEMM_LIB=1``)."""
-    assert act in (None, "gelu"), act
+    assert act is None or (act in ACT_CODES and act != "leaky_relu"), act
     if weight.dtype == torch.float8_e4m3fn:
         if act is not None:
             return linear(x, weight.to(x.dtype), None if bias is None else bias.to(x.dtype), residual, act, out)
@@ -134,6 +137,13 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
         gelu = act == "gelu"
         if gelu:
             epi |= EPI_GELU
+        elif act is not None:
+            if K % 32 or N % 8:      # outside the activation epilogues' domain: GEMM, native activation, add
+                y = activation(linear(x, weight, bias), act, inplace=True)
+                y = y if residual is None else y.add_(residual)
+                return y if out is None else out.view(y.shape).copy_(y)
+            epi |= EPI_GELU | (ACT_CODES[act] << _ACT_SHIFT)
+        act2 = act is not None and not gelu      # one of the newer activations: only the kernels that know the code
         w = weight if weight.is_contiguous() else weight.contiguous()
         dst = out
         if dst is not None:
@@ -145,7 +155,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
             o = dst if dst is not None else torch.empty((M, N), device=x.device, dtype=x.dtype)
             if isinstance(variant, str):                       # split-K (batch-1 grids)
                 return _splitk_run(a, w, o, bias, r, None, None, M, N, K, epi, variant)
-            if (final and row_stats and variant in (6, 19, 20) and not gelu and N % 160 == 0 and K % 64 == 0
+            if (final and row_stats and variant in (6, 19, 20) and act is None and N % 160 == 0 and K % 64 == 0
                     and K >= 128 and _RSO and _native.has_kernel("cgs_gemm_bf16_rowstats_v")):
                 part = torch.empty((M, N // 80, 2), device=x.device, dtype=torch.float32)
                 _check(_lib().cgs_gemm_bf16_rowstats_v(a.data_ptr(), w.data_ptr(), o.data_ptr(), _ptr(bias), _ptr(r),
@@ -154,7 +164,8 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
                        "cgs_gemm_bf16_rowstats_v")
                 rs_part.append(part)
                 return o
-            if M <= 128 and variant in (-1, -2) and K % 32 == 0 and (a.data_ptr() | w.data_ptr()) % 16 == 0:
+            if (M <= 128 and variant in (-1, -2) and K % 32 == 0 and (a.data_ptr() | w.data_ptr()) % 16 == 0
+                    and not act2):     # (the split-K reduce knows the erf GELU only)
                 ws = _skinny_ws(M, N, K, x.device)     # split-K slices when N / 16 workgroups underfill
                 if ws is not None:
                     _check(_lib().cgs_gemm_skinny_ws(a.data_ptr(), w.data_ptr(), o.data_ptr(), _ptr(bias), _ptr(r),
@@ -179,7 +190,16 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
         choice = "hip"
         # M <= 128 (one prompt through CLIP, time-embedding projections): the skinny kernel ("hip" ->
         # auto), weight-bandwidth bound; the big-tile kernels are not candidates there
-        if M * N * K >= (1 << 27) and (M > 128 or K % 32):
+        if act2 and M * N * K >= (1 << 27) and M > 128:
+            cands = []
+            if K % 64 == 0 and K >= 128:
+                cands.append(("v6", lambda: run_hip(6)))
+            cands += [("v4", lambda: run_hip(4)), ("v8", lambda: run_hip(8))]
+            if _underfilled(M, N):
+                cands += [(f"v{v}", (lambda v=v: run_hip(v))) for v in _SMALL_TILE]
+            cands.append(("hip", lambda: run_hip(-1)))
+            choice = autotune.choose(("gemm", M, N, K, epi), cands, default="hip")
+        elif not act2 and M * N * K >= (1 << 27) and (M > 128 or K % 32):
             cands = []
             if K % 64 == 0 and N % 8 == 0:
                 if K >= 128 and not gelu:
@@ -211,6 +231,8 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
             count("gemm", "lib")     # explicit opt-in (CGS_GEMM_LIB=1)
             return run_lib().view(*x.shape[:-1], N)
         count("gemm", "hip")
+        if act is not None:
+            count("act_fused", "hip")
         variant = choice if choice in _SPLITK else {"v7": 7, "v6": 6, "v5": 5, "v4": 4, "v8": 8, "w6": W6,
                                                     "w6n160": W6_160, "v6m128": V6_M128, "v6w4": V6_W4,
                                                     **_SMALL_NAMES}.get(choice, -2)
@@ -226,15 +248,15 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
         vendor_fallback("gemm", f"dtype {x.dtype}/{weight.dtype}, K={x.shape[-1]}")
     if be == "torch":
         y = F.linear(x.float(), weight.float(), None if bias is None else bias.float())
-        if act == "gelu":
-            y = F.gelu(y)
+        if act is not None:
+            y = _act_torch(y, act)
         if residual is not None:
             y = y + residual.float()
         y = y.to(x.dtype)
     else:
         y = F.linear(x, weight, bias)
-        if act == "gelu":
-            y = F.gelu(y)
+        if act is not None:
+            y = _act_torch(y, act)
         if residual is not None:
             y = y + residual
     if out is not None:
@@ -850,12 +872,16 @@ def _spatial():
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, stride=1, padding=0,
            residual: torch.Tensor | None = None, weight_nhwc: torch.Tensor | None = None,
            groups: int = 1, upsample2x: bool = False, x2: torch.Tensor | None = None,
-           gn_stats: bool = False) -> torch.Tensor:
+           gn_stats: bool = False, act: str | None = None, act_param: float = 0.0) -> torch.Tensor:
     """2-D convolution; inside a row-sharded UNet call (latency mode, parallel/spatial.py) the halo rows
     come from the neighbouring ranks and the residual is added to the kept interior. ``gn_stats``: when the
     shape runs on the v6 kernel, its epilogue also writes GroupNorm statistics partials of the output
     (per image, 64-pixel block and channel), attached as ``y._cgs_gnpart`` -- ``group_norm`` over y then
-    skips its statistics pass."""
+    skips its statistics pass. ``act`` (a name of ``ACT_CODES``; ``act_param``: the leaky_relu slope):
+    y = act(conv(x) + bias) (+ residual), see ``_conv2d_act``."""
+    if act is not None:
+        return _conv2d_act(x, weight, bias, stride, padding, residual, weight_nhwc, groups, upsample2x, x2, act,
+                           float(act_param))
     sc = _spatial()
     if sc is None:
         return _conv2d(x, weight, bias, stride, padding, residual, weight_nhwc, groups, upsample2x, x2, gn_stats)
@@ -866,6 +892,65 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, str
     if residual is not None:
         y = y + residual
     return y.contiguous(memory_format=torch.channels_last) if y.is_cuda else y
+
+
+_FUSED_ACT_CONV = {"v3": 3, "v4": 4, "v8": 8}     # the mc::tile convs: their epilogue carries the activation
+
+
+def _conv2d_act(x, weight, bias, stride, padding, residual, weight_nhwc, groups, upsample2x, x2, act, act_param):
+    """act(conv(x) + bias) (+ residual): the activation before the residual add, as the GEMM epilogues do.
+
+    Device, bf16, Cin % 32 == 0, Cout % 8 == 0 and > 16: the autotuner picks among the fused mc::tile convs
+    (cgs_conv2d_nhwc_act, variants 3 / 4 / 8; with ``upsample2x`` or the dual-source ``x2`` too) and
+    ``"split"`` -- the plain conv by its own tuned choice, then the native in-place activation. ``"split"``
+    is the default (and what graph capture gets), and the only form everywhere else: the row-sharded call,
+    fp32, narrow outputs, the CPU."""
+    if act not in ACT_CODES:
+        raise ValueError(f"unknown activation {act!r} (one of {sorted(ACT_CODES)})")
+    st = stride[0] if isinstance(stride, (tuple, list)) else stride
+    pd = padding[0] if isinstance(padding, (tuple, list)) else padding
+
+    def split():
+        y = conv2d(x, weight, bias, st, pd, weight_nhwc=weight_nhwc, groups=groups, upsample2x=upsample2x, x2=x2)
+        y = activation(y, act, act_param, inplace=True)
+        return y if residual is None else y + residual.to(y.dtype)
+
+    Cout, _, kh, kw = weight.shape
+    C1 = x.shape[1]
+    C2 = 0 if x2 is None else x2.shape[1]
+    Cin = C1 + C2
+    if not (_spatial() is None and backend_for("conv", x, "cgs_conv2d_nhwc") == "hip" and groups == 1
+            and x.dtype == torch.bfloat16 and weight_nhwc is not None and x.dim() == 4 and Cin % 32 == 0
+            and Cout % 8 == 0 and Cout > 16 and _native.has_kernel("cgs_conv2d_nhwc_act")
+            and (x2 is None or (C1 % 32 == 0 and x2.dtype == x.dtype and not upsample2x))):
+        return split()
+    N, _, H, W = x.shape
+    Hl, Wl = (2 * H, 2 * W) if upsample2x else (H, W)
+    Ho = (Hl + 2 * pd - kh) // st + 1
+    Wo = (Wl + 2 * pd - kw) // st + 1
+    flags = 16 if upsample2x else 0
+
+    def fused(variant):
+        xc = x.contiguous(memory_format=torch.channels_last)
+        x2c = None if x2 is None else x2.contiguous(memory_format=torch.channels_last)
+        r = None if residual is None else residual.contiguous(memory_format=torch.channels_last)
+        out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+        _check(_lib().cgs_conv2d_nhwc_act(xc.data_ptr(), _ptr(x2c), C1, weight_nhwc.data_ptr(), _ptr(bias), _ptr(r),
+                                          out.data_ptr(), N, H, W, Cin, Cout, kh, kw, st, pd, Ho, Wo, flags,
+                                          variant, ACT_CODES[act], act_param, _stream()), "cgs_conv2d_nhwc_act")
+        return out
+
+    # ("split" is timed last: whatever the first candidate of a tuning pass pays for a cold start, the form
+    # that can never lose to conv + a separate activation pass does not pay it)
+    cands = [(n, (lambda v=v: fused(v))) for n, v in _FUSED_ACT_CONV.items()] + [("split", split)]
+    choice = autotune.choose(("conv", N, H, W, Cin, Cout, kh, st, pd, flags, int(residual is not None))
+                             + ((("dual", C1),) if x2 is not None else ()) + ("act", act, act_param),
+                             cands, default="split")
+    if choice == "split":
+        return split()
+    count("conv", "hip")
+    count("act_fused", "hip")
+    return fused(_FUSED_ACT_CONV[choice])
 
 
 def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, stride=1, padding=0,
@@ -1094,8 +1179,57 @@ def silu(x: torch.Tensor) -> torch.Tensor:
     return F.silu(x.float()).to(x.dtype) if x.device.type == "cpu" else F.silu(x)
 
 
+# The activation set of ``activation`` and of the fused linear / conv2d epilogues: name -> CgsAct code
+# (csrc/kernels/common.h). ``leaky_relu`` takes one parameter, its negative slope.
+ACT_CODES = {"gelu": 1, "gelu_tanh": 2, "gelu_pytorch_tanh": 2, "quick_gelu": 3, "silu": 4, "relu": 5,
+             "leaky_relu": 6}
+_ACT_SHIFT = 8     # GEMM epilogue flags: EPI_GELU | code << 8 (EPI_GELU alone = erf GELU)
+
+
+def _act_torch(y: torch.Tensor, act: str, param: float = 0.0) -> torch.Tensor:
+    """The torch definition of each activation (the CPU / reference path; the expressions the models used
+    before the activations moved into the ops, so fp32 CPU results are unchanged)."""
+    if act == "gelu":
+        return F.gelu(y)
+    if act in ("gelu_tanh", "gelu_pytorch_tanh"):
+        return F.gelu(y, approximate="tanh")
+    if act == "quick_gelu":
+        return y * torch.sigmoid(1.702 * y)
+    if act == "silu":
+        return F.silu(y)
+    if act == "relu":
+        return torch.relu(y)
+    if act == "leaky_relu":
+        return F.leaky_relu(y, param)
+    raise ValueError(f"unknown activation {act!r} (one of {sorted(ACT_CODES)})")
+
+
+def activation(x: torch.Tensor, act: str, param: float = 0.0, inplace: bool = False) -> torch.Tensor:
+    """y = act(x) for the set in ``ACT_CODES`` (``param``: the leaky_relu slope); ``inplace`` writes into x.
+    Device: one HIP kernel (cgs_act, 16-byte vectors) for bf16 / fp16 / fp32; CPU: fp32 math, cast back."""
+    if act not in ACT_CODES:
+        raise ValueError(f"unknown activation {act!r} (one of {sorted(ACT_CODES)})")
+    be = backend_for("act", x, "cgs_act")
+    if be == "hip" and x.dtype in _DT:
+        count("act", "hip")
+        dense = x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))
+        src = x if dense and x.data_ptr() % 16 == 0 else x.contiguous().clone()
+        y = src if (inplace or src is not x) else torch.empty_like(src)
+        _check(_lib().cgs_act(src.data_ptr(), y.data_ptr(), src.numel(), ACT_CODES[act], float(param), _DT[x.dtype],
+                              _stream()), "cgs_act")
+        if inplace and y is not x:
+            x.copy_(y)
+            return x
+        return y
+    y = _act_torch(x.float(), act, param).to(x.dtype) if x.device.type == "cpu" else _act_torch(x, act, param)
+    if inplace:
+        x.copy_(y)
+        return x
+    return y
+
+
 def gelu(x: torch.Tensor, approximate: str = "none") -> torch.Tensor:
-    return F.gelu(x, approximate=approximate)
+    return activation(x, "gelu_tanh" if approximate == "tanh" else "gelu")
 
 
 def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0,

@@ -54,11 +54,14 @@ def _f32(t, device):
     return t
 
 
-def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, residual=None, gelu=False,
+def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, residual=None, gelu=False, act_code=0,
          alpha=1.0, bkn=False, batch=1, sab=0, sbb=0, scb=0, M=None, N=None, K=None,
          lda=None, ldb=None, ldc=None, ldr=0):
-    """Raw launch of ``cgs_gemm_f32`` on fp32 operands (strides in elements)."""
+    """Raw launch of ``cgs_gemm_f32`` on fp32 operands (strides in elements). ``act_code``: a CgsAct code
+    (``ops.core.ACT_CODES``) applied where ``gelu`` applies the erf GELU."""
     epi = (_BIAS if bias is not None else 0) | (_RES if residual is not None else 0) | (_GELU if gelu else 0)
+    if act_code:
+        epi |= _GELU | (act_code << 8)
     _check(_lib().cgs_gemm_f32(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias), _ptr(residual),
                                M, N, K, lda, ldb, ldc, ldr, epi, float(alpha), 1 if bkn else 0, batch, sab, sbb,
                                scb, _stream()), "cgs_gemm_f32")
@@ -86,7 +89,8 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias, residual, act, out):
         if not r.is_contiguous():
             r = r.contiguous()
     y = out if out is not None else torch.empty((M, N), device=x.device, dtype=F32)
-    gemm(a, w, y, bias=b, residual=r, gelu=act == "gelu", M=M, N=N, K=K, lda=a.stride(0), ldb=w.stride(0), ldc=N,
+    from .core import ACT_CODES
+    gemm(a, w, y, bias=b, residual=r, gelu=act == "gelu", act_code=0 if act in (None, "gelu") else ACT_CODES[act], M=M, N=N, K=K, lda=a.stride(0), ldb=w.stride(0), ldc=N,
          ldr=N if r is not None else 0)
     return y.view(*x.shape[:-1], N)
 
