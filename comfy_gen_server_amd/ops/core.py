@@ -847,6 +847,12 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor | None, bias: torch.Tensor 
             return y
     if be == "hip" and x.dtype in (torch.bfloat16, torch.float16) and C % 8 == 0:
         count("layernorm", "hip")
+        # the kernel reads weight / bias as contiguous rows in the activation dtype: cast fp8 / fp32 / offloaded /
+        # strided params, each on its own (a bias may differ from a weight that already matches)
+        if weight is not None and (weight.dtype != x.dtype or weight.device != x.device or not weight.is_contiguous()):
+            weight = weight.to(device=x.device, dtype=x.dtype).contiguous()
+        if bias is not None and (bias.dtype != x.dtype or bias.device != x.device or not bias.is_contiguous()):
+            bias = bias.to(device=x.device, dtype=x.dtype).contiguous()
         xc = x.contiguous()
         y = torch.empty_like(xc)
         rows = xc.numel() // C

@@ -1,16 +1,21 @@
 """Self-test of tests/_bounds.py on the CPU: a plain emulation of what the kernels compute (fp32 accumulate, one
 bf16 round; for attention a 64-key-tile online softmax with bf16 P) stays inside the bound in every element, and
 each of a set of injected faults -- every one of them under the 1e-2 (attention 2e-2) Frobenius-norm threshold
-of the older kernel tests -- is rejected by assert_within."""
+of the older kernel tests -- is rejected by assert_within. The norm, depthwise and softmax2 bounds are checked in
+bf16 and fp16 against emulations of the kernels' own algorithms (shifted block sums and Chan merges for GroupNorm,
+two passes for LayerNorm)."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from _bounds import assert_within, attention_bound, conv_bound, geglu_bound, gemm_bound, lnfold_bound, rel
+from _bounds import (affine_layernorm_bound, assert_within, attention_bound, conv_bound, dwconv_bound, geglu_bound,
+                     gemm_bound, groupnorm_apply_bound, groupnorm_bound, groupnorm_stats_bound, layernorm_bound,
+                     layernorm_stats_bound, lnfold_bound, rel, rs_from_partials_bound, softmax2_bound)
 
 BF = torch.bfloat16
+DTYPES = [torch.bfloat16, torch.float16]
 GEMM_SHAPES = [(33, 40, 32), (300, 320, 640), (129, 136, 192), (257, 264, 5120)]
 FAULT_SHAPES = [(300, 320, 640), (512, 328, 1280), (257, 264, 5120)]     # large enough for the norm to hide the fault
 
@@ -238,3 +243,328 @@ def test_attention_faults():
     # a split partial kept in bf16 needs its extra rounding: two 64-key slices merged by log-sum-exp
     ref1, tol1 = attention_bound(q, k, v, H, extra_roundings=1)
     assert torch.equal(ref, ref1) and bool((tol1 > tol).all())
+
+
+# ------------------------------------------------------------------------------------------------ GroupNorm
+SPIKE = 48.0
+
+
+def _gn_inputs(N, C, H, W, G, dtype, ppb, shift=1.0, seed=0, narrow=False):
+    """x NCHW (a view of NHWC rows) = 3 randn + shift with a spike at the last pixel of every statistics block (one
+    channel of the first and of the last group), at the first and last element of every image's first and last
+    row; gamma, beta, and pre_add as columns 104 .. 104 + C of a [N, 1000 + C] tensor. narrow: gamma within 3 %
+    of 1 and a pre_add of 0.03 randn, so that a misplaced vector of either stays under the Frobenius threshold."""
+    g = torch.Generator().manual_seed(seed)
+    HW = H * W
+    xr = torch.randn(N, HW, C, generator=g) * 3 + shift
+    for p in list(range(ppb - 1, HW, ppb)) + [HW - 1]:
+        xr[:, p, 0] = SPIKE
+        xr[:, p, C - 1] = -SPIKE
+    xr[:, 0, 0] = xr[:, -1, -1] = SPIKE
+    xr[:, 0, -1] = xr[:, -1, 0] = -SPIKE
+    x = xr.to(dtype).reshape(N, H, W, C).permute(0, 3, 1, 2)
+    w = (1 + 0.03 * torch.randn(C, generator=g) if narrow else torch.randn(C, generator=g) + 1).to(dtype)
+    b = torch.randn(C, generator=g).to(dtype)
+    wide = (torch.randn(N, 1000 + C, generator=g) * (0.03 if narrow else 1.0)).to(dtype)
+    return x, w, b, wide, wide[:, 104:104 + C]
+
+
+def _emulate_gn(x, G, w, b, eps, silu, pre, ppb, fault=None, wide=None):
+    """What the GroupNorm kernels compute, in fp32: per pixel block and channel the sums of d = x - (the block's
+    first pixel) -> (mean, M2); Chan merge over blocks and channels per group; a = rstd gamma, b = (pre - mean) a
+    + beta; x a + b; sigmoid; one round. fault: 'coef' the first row of every image n > 0 takes image n - 1's
+    (a, b); 'tail' the last pixel of the last block left out; 'gamma' the last 8-channel vector takes its
+    neighbour's gamma; 'pld' the pre_add row of image n > 0 read at n * C instead of n * stride out of ``wide``."""
+    dt = x.dtype
+    N, C, H, W = x.shape
+    HW, Cg = H * W, C // G
+    xf = x.float().permute(0, 2, 3, 1).reshape(N, HW, C)
+    pr = torch.zeros(N, C) if pre is None else pre.float()
+    if fault == "pld":
+        flat = wide.float().reshape(-1)
+        pr = torch.stack([flat[104 + n * C:104 + (n + 1) * C] for n in range(N)])
+    nb = (HW + ppb - 1) // ppb
+    cnt, mean, m2 = torch.zeros(N, G), torch.zeros(N, G), torch.zeros(N, G)
+    for bi in range(nb):
+        blk = xf[:, bi * ppb:min(HW, (bi + 1) * ppb)]
+        if fault == "tail" and bi == nb - 1 and blk.shape[1] > 1:
+            blk = blk[:, :-1]
+        c = float(blk.shape[1])
+        d = blk - blk[:, :1]
+        s1, s2 = d.sum(1), (d * d).sum(1)
+        bm = (blk[:, 0] + s1 / c + pr).reshape(N, G, Cg)
+        bq = (s2 - s1 * s1 / c).clamp_min(0).reshape(N, G, Cg)
+        for cc in range(Cg):
+            nn = cnt + c
+            dd, f = bm[:, :, cc] - mean, c / nn
+            mean = mean + dd * f
+            m2 = m2 + bq[:, :, cc] + dd * dd * cnt * f
+            cnt = nn
+    rstd = torch.rsqrt((m2 / cnt).clamp_min(0) + eps)
+    gm = torch.ones(C) if w is None else w.float().clone()
+    bt = torch.zeros(C) if b is None else b.float()
+    if fault == "gamma":
+        gm[-8:] = gm[-16:-8]
+    a = rstd.repeat_interleave(Cg, 1) * gm[None]
+    bb = (pr - mean.repeat_interleave(Cg, 1)) * a + bt[None]
+    A, B = a[:, None, :].expand(N, HW, C).clone(), bb[:, None, :].expand(N, HW, C).clone()
+    if fault == "coef":
+        A[1:, 0], B[1:, 0] = a[:-1], bb[:-1]
+    f = xf * A + B
+    if silu:
+        f = f * torch.sigmoid(f)
+    return f.to(dt).reshape(N, H, W, C).permute(0, 3, 1, 2), torch.stack([mean, m2], -1), torch.stack([mean, rstd], -1)
+
+
+GN_EMU_SHAPES = [(2, 64, 13, 15, 32, 64, 1.0), (5, 320, 13, 15, 32, 16, 1.0), (2, 520, 9, 9, 8, 64, 8.0),
+                 (2, 128, 16, 16, 32, 64, 40.0), (2, 64, 1, 3, 32, 64, 1.0)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("silu", [False, True])
+@pytest.mark.parametrize("N,C,H,W,G,ppb,shift", GN_EMU_SHAPES)
+def test_groupnorm_emulation_within_bound(N, C, H, W, G, ppb, shift, silu, dtype):
+    x, w, b, wide, pre = _gn_inputs(N, C, H, W, G, dtype, ppb, shift)
+    what = f"emulated groupnorm {N}x{C}x{H}x{W} G={G} silu={silu} {dtype}"
+    for pa in (None, pre):
+        y, stats, mr = _emulate_gn(x, G, w, b, 1e-5, silu, pa, ppb)
+        ref, tol = groupnorm_bound(x, G, w, b, 1e-5, silu, pa, ppb=ppb)
+        assert_within(y, ref, tol, what + f" pre={pa is not None}")
+        ref, tol = groupnorm_stats_bound(x, G, pa, ppb=ppb)
+        assert_within(stats, ref, tol, what + " (mean, M2)")
+        ref, tol = groupnorm_apply_bound(x, G, w, b, mr, silu, pa)
+        assert_within(y, ref, tol, what + " apply")
+    C1 = C // 2 - C // 2 % 8
+    ref2, tol2 = groupnorm_bound(x[:, :C1], G, w, b, 1e-5, silu, pre, x2=x[:, C1:])
+    ref, tol = groupnorm_bound(x, G, w, b, 1e-5, silu, pre)
+    assert torch.equal(ref, ref2) and torch.equal(tol, tol2)
+
+
+GN_FAULT_SHAPES = [(3, 320, 24, 24, 32, 64), (4, 128, 28, 28, 32, 64)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("fault", ["coef", "tail", "gamma", "pld"])
+@pytest.mark.parametrize("N,C,H,W,G,ppb", GN_FAULT_SHAPES)
+def test_groupnorm_faults(N, C, H, W, G, ppb, fault, dtype):
+    x, w, b, wide, pre = _gn_inputs(N, C, H, W, G, dtype, ppb, narrow=True)
+    ref, tol = groupnorm_bound(x, G, w, b, 1e-5, True, pre, ppb=ppb)
+    y, stats, mr = _emulate_gn(x, G, w, b, 1e-5, True, pre, ppb, fault=fault, wide=wide)
+    assert rel(y, ref) < 1e-2
+    _rejected(y, ref, tol, f"groupnorm {N}x{C}x{H}x{W} {dtype}: fault {fault}")
+    if fault == "tail":
+        ref, tol = groupnorm_stats_bound(x, G, pre, ppb=ppb)
+        _rejected(stats, ref, tol, f"groupnorm (mean, M2) {N}x{C}x{H}x{W} {dtype}: fault {fault}")
+    if fault in ("coef", "gamma"):              # faults of the apply pass: its own (mean, rstd) are what it was given
+        ref, tol = groupnorm_apply_bound(x, G, w, b, mr, True, pre)
+        _rejected(y, ref, tol, f"groupnorm apply {N}x{C}x{H}x{W} {dtype}: fault {fault}")
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm
+def _ln_inputs(rows, C, dtype, mean=0.5, spread=2.0, spike=SPIKE, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(rows, C, generator=g) * spread + mean
+    if spike:
+        x[:, 0] = mean + spike
+        x[:, -1] = mean - spike
+    return x.to(dtype), (torch.randn(C, generator=g) + 1).to(dtype), torch.randn(C, generator=g).to(dtype)
+
+
+def _emulate_ln(x, w, b, eps, fault=None):
+    """Two-pass fp32 LayerNorm, one round. fault: 'chunk' the last 8 elements missing from both sums; 'onepass'
+    the variance as E[x^2] - mean^2."""
+    xf = x.float()
+    C = x.shape[-1]
+    xs = xf[:, :-8] if fault == "chunk" else xf
+    m = xs.sum(-1, keepdim=True) / C
+    if fault == "onepass":
+        q = ((xf * xf).sum(-1, keepdim=True) / C - m * m).clamp_min(0)
+    else:
+        q = ((xs - m) ** 2).sum(-1, keepdim=True) / C
+    r = torch.rsqrt(q + eps)
+    f = (xf - m) * r
+    if w is not None:
+        f = f * w.float()
+    if b is not None:
+        f = f + b.float()
+    return f.to(x.dtype), torch.cat([m, r], -1)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C,mean,spread", [(8, 0.5, 2.0), (72, 40.0, 2.0), (520, 0.5, 2.0), (2048, 200.0, 0.5),
+                                           (5120, 0.5, 2.0)])
+def test_layernorm_emulation_within_bound(C, mean, spread, dtype):
+    x, w, b = _ln_inputs(33, C, dtype, mean, spread)
+    for wi, bi in ((w, b), (w, None), (None, None)):
+        y, rs = _emulate_ln(x, wi, bi, 1e-5)
+        ref, tol = layernorm_bound(x, wi, bi, 1e-5)
+        assert_within(y, ref, tol,
+                      f"emulated layernorm C={C} mean {mean} {dtype} w={wi is not None} b={bi is not None}")
+    ref, tol = layernorm_stats_bound(x, 1e-5)
+    assert_within(rs, ref, tol, f"emulated layernorm (mean, rstd) C={C} mean {mean} {dtype}")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C", [2048, 4096])
+def test_layernorm_fault_last_chunk_missing(C, dtype):
+    x, w, b = _ln_inputs(64, C, dtype, spike=0.0)
+    ref, tol = layernorm_bound(x, w, b, 1e-5)
+    y, rs = _emulate_ln(x, w, b, 1e-5, fault="chunk")
+    assert rel(y, ref) < 1e-2
+    _rejected(y, ref, tol, f"layernorm C={C} {dtype}: last chunk missing from the sums")
+    ref, tol = layernorm_stats_bound(x, 1e-5)
+    _rejected(rs, ref, tol, f"layernorm (mean, rstd) C={C} {dtype}: last chunk missing from the sums")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C", [72, 2048])
+def test_layernorm_fault_one_pass_variance(C, dtype):
+    """E[x^2] - mean^2 in fp32 on rows of mean 200, spread 0.5: x^2 = 4e4 carries 2.4e-3 of rounding each against
+    a variance of 0.25."""
+    x, w, b = _ln_inputs(64, C, dtype, mean=200.0, spread=0.5, spike=0.0)
+    ref, tol = layernorm_bound(x, w, b, 1e-5)
+    y, rs = _emulate_ln(x, w, b, 1e-5, fault="onepass")
+    assert rel(y, ref) < 1e-2
+    _rejected(y, ref, tol, f"layernorm C={C} {dtype}: one-pass variance")
+    ref, tol = layernorm_stats_bound(x, 1e-5)
+    _rejected(rs, ref, tol, f"layernorm (mean, rstd) C={C} {dtype}: one-pass variance")
+
+
+def _partials(x, P):
+    """fp64 (mean, M2) of the P groups of 80 columns of x [M, 80 P], as the fp32 tensor the kernel reads."""
+    xg = x.double().reshape(x.shape[0], P, 80)
+    m = xg.mean(-1)
+    return torch.stack([m, ((xg - m[..., None]) ** 2).sum(-1)], -1).float()
+
+
+def _emulate_rs_from_partials(part, eps, skip_last=False):
+    n, mean, m2 = 80.0, part[:, 0, 0].clone(), part[:, 0, 1].clone()
+    for c in range(1, part.shape[1] - (1 if skip_last else 0)):
+        nn = n + 80.0
+        d, f = part[:, c, 0] - mean, 80.0 / nn
+        mean = mean + d * f
+        m2 = m2 + part[:, c, 1] + d * d * n * f
+        n = nn
+    return torch.stack([mean, torch.rsqrt(m2 / n + eps)], -1)
+
+
+@pytest.mark.parametrize("P", [1, 2, 3, 8, 18])
+@pytest.mark.parametrize("mean", [0.5, 40.0])
+def test_rs_from_partials_emulation_and_fault(P, mean):
+    x, _, _ = _ln_inputs(65, 80 * P, torch.bfloat16, mean=mean)
+    part = _partials(x, P)
+    ref, tol = rs_from_partials_bound(part, 1e-5)
+    assert_within(_emulate_rs_from_partials(part, 1e-5), ref, tol, f"emulated rs from {P} partials, mean {mean}")
+    full, _ = layernorm_stats_bound(x, 1e-5)
+    assert (ref - full).abs().max().item() < 1e-4 * max(1.0, mean)       # the partials stand for the whole row
+    if P > 2 and mean == 40.0:                   # from 3 partials on the skipped one stays under the norm threshold
+        bad = _emulate_rs_from_partials(part, 1e-5, skip_last=True)
+        assert rel(bad, ref) < 1e-2
+        _rejected(bad, ref, tol, f"rs from {P} partials: last one skipped")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_affine_layernorm_emulation_and_fault(dtype):
+    N, HW, C = 3, 35, 1280
+    g = torch.Generator().manual_seed(0)
+    x = (torch.randn(N, HW, C, generator=g) * 2 + 0.5).to(dtype)
+    co = (torch.randn(N, 2 * C, generator=g) * 0.05).to(dtype)
+    sc, sh = co[:, :C], co[:, C:]
+
+    def emulate(fault):
+        a = (1.0 + sc.float())[:, None, :].expand(N, HW, C).clone()
+        if fault:
+            a[1:, 0] = (1.0 + sc.float())[:-1]                      # the first row of image n takes image n - 1's scale
+        xa = torch.addcmul(sh.float()[:, None, :], x.float(), a).to(dtype)
+        return xa, _emulate_ln(xa.reshape(-1, C), None, None, 1e-6)[0].reshape(N, HW, C)
+
+    xa, y = emulate(False)
+    xa_ref, xa_tol, y_ref, y_tol = affine_layernorm_bound(x, sc, sh, 1.0, 1e-6, xa)
+    assert_within(xa, xa_ref, xa_tol, f"emulated affine layernorm xa {dtype}")
+    assert_within(y, y_ref, y_tol, f"emulated affine layernorm y {dtype}")
+    xa, y = emulate(True)
+    assert rel(xa, xa_ref) < 1e-2
+    _rejected(xa, xa_ref, xa_tol, f"affine layernorm {dtype}: one row with the previous image's scale")
+
+
+# ------------------------------------------------------------------------------------------------ depthwise conv
+def _dw_inputs(N, H, W, C, k, dtype, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(N, H, W, C, generator=g) + 0.5).to(dtype)
+    w = (torch.randn(k * k, C, generator=g) / k).to(dtype)
+    return x, w, torch.randn(C, generator=g).to(dtype)
+
+
+def _emulate_dw(x, w, b, k, replicate):
+    C = x.shape[-1]
+    xp = F.pad(x.float().permute(0, 3, 1, 2), (k // 2,) * 4, mode="replicate" if replicate else "constant")
+    y = F.conv2d(xp, w.float().t().reshape(C, 1, k, k), None if b is None else b.float(), 1, 0, 1, C)
+    return y.permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("k", [3, 7])
+@pytest.mark.parametrize("replicate", [False, True])
+def test_dwconv_emulation_within_bound(k, replicate, dtype):
+    x, w, b = _dw_inputs(2, 5, 6, 64, k, dtype)
+    for bias in (b, None):
+        ref, tol = dwconv_bound(x, w, bias, k, replicate)
+        y = _emulate_dw(x, w, bias, k, replicate).to(dtype)
+        assert_within(y, ref, tol, f"emulated dwconv k={k} replicate={replicate} bias={bias is not None} {dtype}")
+    ref, tol = layernorm_stats_bound(y.reshape(-1, 64), 1e-6)
+    rs = _emulate_ln(y.reshape(-1, 64), None, None, 1e-6)[1]
+    assert_within(rs, ref, tol, f"emulated dwconv row statistics {dtype}")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_dwconv_fault_border_tap_replicated(dtype):
+    """Tap (-1, -1) of output pixel (0, 0) of the last image reads pixel (0, 0) instead of zero."""
+    x, w, b = _dw_inputs(3, 24, 24, 64, 3, dtype)
+    ref, tol = dwconv_bound(x, w, b, 3, False)
+    y = _emulate_dw(x, w, b, 3, False)
+    y[-1, 0, 0] += x[-1, 0, 0].float() * w[0].float()
+    assert rel(y.to(dtype), ref) < 1e-2
+    _rejected(y.to(dtype), ref, tol, f"dwconv {dtype}: one border tap replicated")
+
+
+# ------------------------------------------------------------------------------------------------ softmax2
+def _sm2_inputs(rows, cols, seed=0):
+    """Rows of 6 randn in log2 units: a spike in the last column, a constant row, a row with -inf entries, a row
+    of magnitude 1e4."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(rows, cols, generator=g) * 6
+    x[:, -1] += 30
+    x[0] = 3.0
+    x[1, ::2] = -math.inf
+    x[2] = torch.randn(cols, generator=g) * 1e4
+    x[3] = 1e4 + torch.randn(cols, generator=g)
+    return x
+
+
+def _emulate_sm2(x, drop=0):
+    p = torch.exp2(x - x.amax(-1, keepdim=True))
+    s = (p[:, :-drop] if drop else p).sum(-1, keepdim=True)
+    return (p * (1.0 / s)).to(BF)
+
+
+@pytest.mark.parametrize("cols", [4, 1020, 4100])
+def test_softmax2_emulation_within_bound(cols):
+    x = _sm2_inputs(37, cols)
+    ref, tol = softmax2_bound(x)
+    y = _emulate_sm2(x)
+    assert_within(y, ref, tol, f"emulated softmax2 cols={cols}")
+    assert bool((tol[1, ::2] == 0).all()) and bool((y[1, ::2] == 0).all())
+    y[1, 0] = 1e-30                                                 # a -inf input must give exactly 0
+    _rejected(y, ref, tol, f"softmax2 cols={cols}: a masked entry not 0")
+
+
+def test_softmax2_fault_normaliser_tail_dropped():
+    """The last 4 of 1020 columns, which hold 0.8 % of each row's mass, missing from the normaliser."""
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(37, 1020, generator=g) * 0.25
+    x[:, -4:] += 1.0
+    ref, tol = softmax2_bound(x)
+    assert_within(_emulate_sm2(x), ref, tol, "emulated softmax2 1020")
+    y = _emulate_sm2(x, drop=4)
+    assert rel(y, ref) < 1e-2
+    _rejected(y, ref, tol, "softmax2: the last 4 columns missing from the normaliser")
