@@ -1,5 +1,6 @@
 """Per-element worst-case error bounds of the bf16 GEMM, conv and attention kernels (test_kernel_bounds_*.py) and
-of the bf16 / fp16 GroupNorm, LayerNorm, depthwise-conv and softmax2 kernels (test_norm_bounds_gpu.py).
+of the bf16 / fp16 GroupNorm, LayerNorm, depthwise-conv and softmax2 kernels (test_norm_bounds_gpu.py), of the GRN
+family and of the planar image-space kernels (test_image_bounds_gpu.py).
 
 Every ``*_bound`` function takes the operands the kernel is given (CPU or GPU tensors of any float type), builds
 the result in fp64 and returns ``(ref, tol)``: two fp64 tensors of the output's shape. ``assert_within`` then
@@ -59,6 +60,55 @@ softmax2, p = 2^(x - max) / sum:  tol = u p (1 + 2u) + tiny + (C_ACC cols e + 2 
   the normaliser is an fp32 sum of cols terms, each with the relative error EXP2_REL + |x_j - max| e ln 2 of its own
   (the subtraction is rounded once); weighted by p_j / sum these average to at most EXP2_REL + ln(cols) e <= EXP2_REL
   + 10 e; 4 e for the reciprocal and the product. A -inf input gets ref = tol = 0.
+The GRN family and the image-space kernels (csrc/kernels/image.hip; test_image_bounds_gpu.py). build_native.py
+compiles with -O3 and without -ffast-math or any other relaxed-math flag: sqrtf and / are correctly rounded, one e
+each; fused multiply-adds only remove roundings. The kernels store bf16, fp16 or fp32: u(float32) = e.
+
+GRN statistics, gx[n, c] = sqrt(sum_HW a^2), a = x or gelu(x). Only positive terms, so the error of the sum is
+relative, C_ACC (L + 1) e: L dependent additions and the rounding of a^2. grn_depth restates L from the code:
+  v2   a lane adds every fourth row of its slice (ceil(rows_per / 4), rows_per = ceil(HW / S), S = grn_slices), the
+       LDS merge of the four row groups (2), the finalize loop over S / 4 float4s, each summed as a tree (+ 2);
+  gns  nbk = HW / 64 given partials in four chains (nbk / 4, the tail on the first), then the merge (2);
+  v1   32-row block sums added by atomics in unknown order: L = HW.
+  dgx = gx (C_ACC (L + 1) e / 2 + e) + tiny: the square root halves the relative error and adds a rounding. With the
+  fused GELU, | ||a + d|| - ||a|| | <= ||d|| <= sqrt(HW) GELU_ABS is added as an absolute term -- not a relative one,
+  a channel of large negative x has gx below the approximation error. A channel of zeros is exact (tol = 0):
+  gelu_sig2(0) = 0 * rcp(2) = 0.
+Channel mean, positive terms again: wave_sum (6) and the 4-wave merge (2) give the sum of a block of 256 channels,
+the apply kernel adds ceil(nblk / 64) of those per lane and runs another wave_sum (6): Lm. v1: ceil(C / 256) per
+thread and an 8-level LDS tree.
+  dmean = mean_C dgx + C_ACC Lm e mean;  inv = 1 / (mean + 1e-6):  dinv = inv (dmean / (mean + 1e-6) + 4 e)
+  (the division by C, the addition, the fp32 value of 1e-6f, the reciprocal).
+GRN output y = beta + a (1 + gamma nx), nx = gx inv, dnx = dgx inv + gx dinv + dgx dinv:
+  d = |a gamma| dnx + k e (|beta| + |a| (1 + |gamma nx|)) + [GELU] GELU_ABS |1 + gamma nx|;  tol = _store_dt(ref, d)
+  k = 5 roundings in every form: nx = gx inv, gamma nx, 1 + ., a (.), beta + .. The row-tiled form does the first
+  three once per thread (a_j = 1 + gamma (nx iv)), the grid-stride form and v1 per element: the same count.
+grn_apply_bound: gx and the block sums given, dnx = nx (C_ACC (ceil(nblk / 64) + 6) e + 4 e) only.
+grn_scale_weight_bound, Wn[n] = W (1 + (gamma gx) inv) in bf16: four roundings, d = |W gamma| dnx + 4 e |W| (1 +
+  |gamma nx|) with the dnx of grn_apply_bound.
+resize (bilinear, bicubic, area) is separable: ref = Wy x Wx^T with the weights in fp64 from the exact scale.
+  tol = store + k e sum |w_i x_i| + dw sum |x_taps|
+  The fp32 source coordinate (o + 0.5) scale - 0.5 carries three roundings of values <= max(H, Ho): 3 e max(H, Ho),
+  times the largest slope of the weight in the coordinate: 1 for bilinear, 1.35 for the cubic convolution with A =
+  -0.75 (|cubic1'| at t = 0.6); the cubic's Horner forms add 64 e (six roundings of intermediates <= 8 |A| = 6 at t
+  <= 2). dw is the sum over both axes (the weights of the other axis are <= 1). Both interpolants are continuous
+  across integer source coordinates, so a floor that differs between fp32 and fp64 moves the taps but changes the
+  value by no more than the same coordinate error: it stays inside dw. k = 6 (bilinear: 1 - l, two products and
+  a sum per axis), 10 (bicubic: four products and sums per axis, the weights' last rounding), window size + 1 (area,
+  dw = 0). nearest and nearest-exact move bits: the reference is F.interpolate on the CPU in the same dtype, tol = 0.
+upfirdn2d: an fp64 reference of its own (zero-insert, pad or crop, true convolution, decimate);
+  tol = store + C_ACC kh kw e mag.
+fused_bias_act, leaky(x + b[c]) * scale with slope and scale as the fp32 values the kernel is given: three relative
+  roundings, tol = store + 3 e |ref|.
+softmax_rows, p = __expf(x scale - max) / sum in fp32: the product and the subtraction are rounded once each, the
+  exponent is off by (|x scale| + |t|) e, t = x scale - max; __expf multiplies by the rounded constant log2 e: 2 |t|
+  e more; relative after the exponential, plus EXP2_REL. The normaliser carries the p-weighted mean of the same and
+  C_ACC cols e; 2 e for the reciprocal and the product; the fp32 store e p.
+tome_match, s = (a_i . b_j) inv_a inv_b with inv = rsqrtf(sum of squares):
+  ds = C_ACC (C + 2) e sum |a_i| |b_j| inv_a inv_b + 2 RSQRT_REL |s|
+  the dot product runs over k in sequence, two more products; the second term is the two reciprocal roots (the
+  relative error of their sums of squares, (ceil(C / 64) + 7) e each, is not itemised: for C >= 32 the second half
+  of C_ACC (C + 2) e mag, unused by a sequential sum, majorises it). A row of zeros has inv = 0 and s = 0.
 """
 import math
 
@@ -80,8 +130,8 @@ TINY = {torch.bfloat16: 2.0 ** -126, torch.float16: 2.0 ** -25, torch.float32: 2
 
 
 def u(dtype):
-    """Unit roundoff of a 16-bit storage type."""
-    return {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[dtype]
+    """Unit roundoff of a storage type."""
+    return {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: 2.0 ** -24}[dtype]
 
 
 def f64(t):
@@ -423,3 +473,356 @@ def softmax2_bound(x):
     rel = C_ACC * cols * E + 2 * EXP2_REL + 14 * E + dist * E * math.log(2.0)
     tol = _store_dt(ref, rel * ref, torch.bfloat16)
     return ref, torch.where(torch.isfinite(x), tol, torch.zeros_like(tol))
+
+
+# ------------------------------------------------------------------------------------------------ GRN
+# (N, HW, C) -> the apply form cgs_grn_nhwc_v2 runs at the default cgs_grn_set_rows(1); the smallest shapes that reach
+# N > 4 with a bsum tail and a slice tail, N = GRN_MAXN, both sides of the row-tiled predicate (257 and 204 chunks a
+# row just miss it, 256 and 205 just meet it), idle threads in the last block of a row (461 chunks)
+GRN_V2_SHAPES = {(1, 1, 8): "grid", (5, 35, 264): "grid", (64, 17, 72): "grid", (3, 33, 2056): "grid",
+                 (2, 17, 2048): "rows", (2, 16, 1640): "rows", (2, 33, 3688): "rows", (1, 70, 1632): "grid"}
+GRN_GNS_SHAPES = [(5, 64, 264), (2, 320, 2048)]
+# (input shape, output size) of the resize tests
+RESIZE_CASES = [((2, 3, 5, 7), s) for s in [(1, 1), (9, 4), (5, 7), (13, 16), (1, 16), (9, 1)]] + \
+               [((1, 2, 1, 1), (3, 2)), ((1, 1, 16, 18), (5, 7))]
+RESIZE_MODES = [("nearest", None), ("nearest-exact", None), ("bilinear", False), ("bilinear", True),
+                ("bicubic", False), ("bicubic", True), ("area", None)]
+GRN_MAXN = 64
+GRN_K = 5                # fp32 roundings from (gx, inv) to the value that is stored, the same in every form
+
+
+def grn_slices(N, HW, C):
+    """cgs_grn_slices (image.hip): about 512 pass-1 blocks, at least 16 rows a slice, a multiple of 4."""
+    cb = (C // 8 + 63) // 64
+    s = min((512 + N * cb - 1) // (N * cb), (HW + 15) // 16)
+    return max((s + 3) & ~3, 4)
+
+
+def grn_row_tiled(HW, C, rows=1):
+    """The predicate of grn_apply_launch: the row-tiled apply where at most 20 % of a block's threads idle."""
+    rt = {1: 16, 2: 32}.get(rows, 64)
+    cpr = C // 8
+    groups = (cpr + 255) // 256
+    return bool(rows) and (HW + rt - 1) // rt <= 65535 and cpr * 5 >= groups * 1024
+
+
+def grn_depth(form, N, HW, C):
+    """(L, Lm): the dependent fp32 additions of the sum of squares and of the channel mean (module docstring)."""
+    nblk = (C + 255) // 256
+    Lm = 6 + 2 + (nblk + 63) // 64 + 6
+    if form == "v2":
+        S = grn_slices(N, HW, C)
+        return ((HW + S - 1) // S + 3) // 4 + 2 + S // 4 + 2, Lm
+    if form == "gns":
+        nbk = HW // 64
+        return nbk // 4 + nbk % 4 + 2, Lm
+    assert form == "v1", form
+    return HW, nblk + 8
+
+
+def grn_inputs(N, HW, C, dtype, device="cpu", seed=0):
+    """x [N, HW, C] = randn s_n s_c with s_n log-spaced over 0.05 .. 8 and s_c over 0.03 .. 10, both permuted; the
+    largest s_c is raised until its channel holds nx >= 5 (as far as C allows); one channel of zeros and one of
+    -(6 + |randn|) (its GELU is below GELU_ABS); gamma ~ N(0, 0.5) with three entries at -1 / nx of image 0, where
+    1 + gamma nx passes near 0; beta ~ N(0, 0.1). Returns (x, gamma, beta, (zero channel, negative channel))."""
+    g = torch.Generator().manual_seed(seed)
+    s_n = torch.logspace(math.log10(0.05), math.log10(8.0), N)[torch.randperm(N, generator=g)]
+    if N == 1:
+        s_n = torch.ones(1)
+    s_c = torch.logspace(math.log10(0.03), math.log10(10.0), C)[torch.randperm(C, generator=g)]
+    x = torch.randn(N, HW, C, generator=g) * s_n[:, None, None] * s_c[None, None, :]
+    order = torch.argsort(s_c)
+    cz, cn, ctop = int(order[0]), int(order[1]), int(order[-1])
+    x[:, :, cz] = 0.0
+    x[:, :, cn] = -(6.0 + torch.randn(N, HW, generator=g).abs())
+    if C > 6:                                # nx_top = C g_top / (g_top + rest) >= 6  <=>  g_top >= 6 rest / (C - 6)
+        gn = x.pow(2).sum(1).sqrt()
+        rest = gn.sum(1) - gn[:, ctop]
+        x[:, :, ctop] *= (6 * rest / ((C - 6) * gn[:, ctop].clamp_min(1e-30))).clamp_min(1.0)[:, None]
+    x = x.to(dtype)
+    gx = x.double().pow(2).sum(1).sqrt()
+    nx0 = (gx / (gx.mean(1, keepdim=True) + 1e-6))[0]
+    gamma = torch.randn(C, generator=g) * 0.5
+    for c in torch.argsort(nx0, descending=True)[:3].tolist():
+        if nx0[c] > 0.05:
+            gamma[c] = -1.0 / nx0[c].item()
+    beta = torch.randn(C, generator=g) * 0.1
+    return x.to(device), gamma.to(dtype).to(device), beta.to(dtype).to(device), (cz, cn)
+
+
+def grn_nx(x, pre_gelu=False):
+    """fp64 nx [N, C] of x [N, HW, C]."""
+    a = F.gelu(f64(x)) if pre_gelu else f64(x)
+    gx = a.pow(2).sum(1).sqrt()
+    return gx / (gx.mean(1, keepdim=True) + 1e-6)
+
+
+def _grn_act(x, pre_gelu):
+    x = f64(x)
+    x = x.reshape(x.shape[0], -1, x.shape[-1])
+    return x, (F.gelu(x) if pre_gelu else x)
+
+
+def grn_stats_bound(x, pre_gelu, depth, part=None):
+    """(gx, dgx, inv, dinv): the fp32 gx [N, C] and the per-image inv = 1 / (mean_C gx + 1e-6) [N] with their
+    tolerances. x [N, HW, C] or [N, H, W, C]; depth = grn_depth(form, ...). part [N, nbk, C]: the fp32 block sums of
+    squares the GNS forms are given instead of x."""
+    L, Lm = depth
+    if part is not None:
+        ss = f64(part).sum(1)
+        exact = (f64(part) == 0).all(1)
+        HW = 0
+    else:
+        x, a = _grn_act(x, pre_gelu)
+        HW = x.shape[1]
+        ss = a.pow(2).sum(1)
+        exact = (x == 0).all(1)
+    gx = ss.sqrt()
+    dgx = gx * (0.5 * C_ACC * (L + 1) * E + E) + TINY[torch.float32]
+    if pre_gelu:
+        dgx = dgx + math.sqrt(HW) * GELU_ABS
+    dgx = torch.where(exact, torch.zeros_like(dgx), dgx)
+    mean = gx.mean(1)
+    dmean = dgx.mean(1) + C_ACC * Lm * E * mean
+    inv = 1 / (mean + 1e-6)
+    return gx, dgx, inv, inv * (dmean * inv + 4 * E)
+
+
+def _grn_out(a, gamma, beta, nx, dnx, pre_gelu, k, dtype, shape):
+    g, b = f64(gamma).reshape(1, 1, -1), f64(beta).reshape(1, 1, -1)
+    gn = g * nx[:, None, :]
+    ref = b + a * (1 + gn)
+    d = (a * g).abs() * dnx[:, None, :] + k * E * (b.abs() + a.abs() * (1 + gn.abs()))
+    if pre_gelu:
+        d = d + GELU_ABS * (1 + gn).abs()
+    return ref.reshape(shape), _store_dt(ref, d, dtype).reshape(shape)
+
+
+def grn_bound(x, gamma, beta, pre_gelu, depth, k=GRN_K):
+    """y = beta + a (1 + gamma nx), a = x or gelu(x), with the statistics error of the form that ran."""
+    gx, dgx, inv, dinv = grn_stats_bound(x, pre_gelu, depth)
+    _, a = _grn_act(x, pre_gelu)
+    dnx = dgx * inv[:, None] + gx * dinv[:, None] + dgx * dinv[:, None]
+    return _grn_out(a, gamma, beta, gx * inv[:, None], dnx, pre_gelu, k, x.dtype, x.shape)
+
+
+def _grn_given(gx, bsum=None, inv=None):
+    """nx and dnx from the fp32 gx [N, C] and block sums [N, nblk] a kernel is given (or the inv [N] they stand for)."""
+    gx = f64(gx)
+    C = gx.shape[1]
+    nblk = (C + 255) // 256
+    inv = 1 / (f64(bsum).sum(1) / C + 1e-6) if inv is None else f64(inv)
+    nx = gx * inv[:, None]
+    return nx, nx * (C_ACC * ((nblk + 63) // 64 + 6) * E + 4 * E)
+
+
+def grn_apply_bound(x, gamma, beta, gx, bsum, pre_gelu=False, k=GRN_K):
+    """The apply pass with given fp32 gx [N, C] and bsum [N, ceil(C / 256)]: no statistics term."""
+    nx, dnx = _grn_given(gx, bsum)
+    _, a = _grn_act(x, pre_gelu)
+    return _grn_out(a, gamma, beta, nx, dnx, pre_gelu, k, x.dtype, x.shape)
+
+
+def grn_scale_weight_bound(W, gamma, gx, inv):
+    """Wn [N, O, K] = W (1 + gamma nx_n) in bf16 from the fp32 gx [N, K] and inv [N] = 1 / (mean_K gx + 1e-6) in fp64
+    from the ceil(K / 256) block sums the kernel is given."""
+    nx, dnx = _grn_given(gx, inv=inv)
+    Wd, g = f64(W)[None], f64(gamma).reshape(1, 1, -1)
+    gn = g * nx[:, None, :]
+    ref = Wd * (1 + gn)
+    d = (Wd * g).abs() * dnx[:, None, :] + 4 * E * Wd.abs() * (1 + gn.abs())
+    return ref, _store_dt(ref, d, torch.bfloat16)
+
+
+# ------------------------------------------------------------------------------------------------ resize
+CUBIC_A = -0.75
+CUBIC_SLOPE = 1.35       # max |d w / d t| of the cubic convolution weights with A = -0.75 (cubic1 at t = 0.6)
+CUBIC_ABS = 64 * E       # Horner evaluation of one weight in fp32
+
+
+def _cubic1(t):
+    return ((CUBIC_A + 2) * t - (CUBIC_A + 3)) * t * t + 1
+
+
+def _cubic2(t):
+    return ((CUBIC_A * t - 5 * CUBIC_A) * t + 8 * CUBIC_A) * t - 4 * CUBIC_A
+
+
+def resize_coords(n_in, n_out, mode, align):
+    """fp64 source coordinates of one axis, before any clamp (nearest modes: the value that is floored)."""
+    o = torch.arange(n_out, dtype=torch.float64)
+    if mode in ("bilinear", "bicubic") and align:
+        return o * ((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0)
+    if mode == "nearest":
+        return o * (n_in / n_out)
+    if mode == "nearest-exact":
+        return (o + 0.5) * (n_in / n_out)
+    return (o + 0.5) * (n_in / n_out) - 0.5
+
+
+def _resize_axis(n_in, n_out, mode, align):
+    """(W, S, k, dw) of one axis: weights [n_out, n_in], tap counts, roundings, weight error."""
+    Wm, S = torch.zeros(n_out, n_in, dtype=torch.float64), torch.zeros(n_out, n_in, dtype=torch.float64)
+    if mode == "area":
+        cnt = 0
+        for o in range(n_out):
+            a, b = o * n_in // n_out, -((-(o + 1) * n_in) // n_out)
+            Wm[o, a:b] = 1.0 / (b - a)
+            S[o, a:b] = 1.0
+            cnt = max(cnt, b - a)
+        return Wm, S, cnt, 0.0
+    f = resize_coords(n_in, n_out, mode, align)
+    if mode == "bilinear":
+        f = f.clamp_min(0.0)
+    i0 = torch.floor(f)
+    t = f - i0
+    if mode == "bilinear":
+        taps = [(i0, 1 - t), (i0 + (i0 < n_in - 1), t)]
+        k, dw = 3, 3 * E * max(n_in, n_out)
+    else:
+        taps = [(i0 - 1, _cubic2(t + 1)), (i0, _cubic1(t)), (i0 + 1, _cubic1(1 - t)), (i0 + 2, _cubic2(2 - t))]
+        k, dw = 5, CUBIC_SLOPE * 3 * E * max(n_in, n_out) + CUBIC_ABS
+    rows = torch.arange(n_out)
+    for idx, w in taps:
+        idx = idx.clamp(0, n_in - 1).long()
+        Wm.index_put_((rows, idx), w, accumulate=True)
+        S.index_put_((rows, idx), torch.ones_like(w), accumulate=True)
+    return Wm, S, k, dw
+
+
+def resize_bound(x, size, mode, align=None):
+    """F.interpolate(x [N, C, H, W], size, mode, align_corners) as cgs_resize computes it."""
+    Ho, Wo = size
+    H, W = x.shape[-2:]
+    if mode in ("nearest", "nearest-exact"):
+        ref = f64(F.interpolate(x.cpu(), size=(Ho, Wo), mode=mode).to(x.device))
+        return ref, torch.zeros_like(ref)
+    Wy, Sy, ky, dwy = _resize_axis(H, Ho, mode, bool(align))
+    Wx, Sx, kx, dwx = _resize_axis(W, Wo, mode, bool(align))
+    Wy, Sy, Wx, Sx = (t.to(x.device) for t in (Wy, Sy, Wx, Sx))
+    xd = f64(x)
+    ref = Wy @ xd @ Wx.t()
+    mag = Wy.abs() @ xd.abs() @ Wx.abs().t()
+    taps = Sy @ xd.abs() @ Sx.t()
+    k = ky * kx + 1 if mode == "area" else ky + kx
+    return ref, _store_dt(ref, k * E * mag + (dwy + dwx) * taps, x.dtype)
+
+
+# ------------------------------------------------------------------------------------------------ upfirdn2d
+def upfirdn2d_bound(x, kernel, up, down, pad):
+    """x [N, C, H, W]; kernel [kh, kw]; up = (ux, uy), down = (dx, dy), pad = (px0, px1, py0, py1)."""
+    (ux, uy), (dx, dy), (px0, px1, py0, py1) = up, down, pad
+    N, C, H, W = x.shape
+    kh, kw = kernel.shape
+    xd = f64(x).reshape(N * C, 1, H, W)
+    z = xd.new_zeros(N * C, 1, H * uy, W * ux)
+    z[:, :, ::uy, ::ux] = xd
+    z = F.pad(z, (max(px0, 0), max(px1, 0), max(py0, 0), max(py1, 0)))
+    z = z[:, :, max(-py0, 0):z.shape[2] - max(-py1, 0), max(-px0, 0):z.shape[3] - max(-px1, 0)]
+    w = torch.flip(f64(kernel).to(x.device), [0, 1])[None, None]         # conv2d correlates: flipped = convolution
+    ref = F.conv2d(z, w)[:, :, ::dy, ::dx]
+    mag = F.conv2d(z.abs(), w.abs())[:, :, ::dy, ::dx]
+    shape = (N, C) + tuple(ref.shape[2:])
+    ref, mag = ref.reshape(shape), mag.reshape(shape)
+    return ref, _store_dt(ref, C_ACC * kh * kw * E * mag, x.dtype)
+
+
+# ------------------------------------------------------------------------------------------------ fused_bias_act
+def _f32(v):
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def fused_bias_act_bound(x, bias, slope, scale):
+    """leaky_relu(x + bias[c], slope) * scale with c along dim 1."""
+    xd = f64(x)
+    if bias is not None:
+        xd = xd + f64(bias).reshape(1, -1, *([1] * (x.dim() - 2)))
+    ref = torch.where(xd >= 0, xd, xd * _f32(slope)) * _f32(scale)
+    return ref, _store_dt(ref, 3 * E * ref.abs(), x.dtype)
+
+
+# ------------------------------------------------------------------------------------------------ softmax_rows
+def softmax_rows_bound(x, scale):
+    """fp32 softmax over the last dim of x * scale."""
+    s = f64(x) * _f32(scale)
+    cols = s.shape[-1]
+    t = s - s.amax(-1, keepdim=True)
+    p = torch.exp(t)
+    ref = p / p.sum(-1, keepdim=True)
+    ex = (s.abs() + 3 * t.abs()) * E + EXP2_REL
+    rel = ex + (ref * ex).sum(-1, keepdim=True) + C_ACC * cols * E + 2 * E
+    return ref, E * ref + TINY[torch.float32] + rel * ref
+
+
+# ------------------------------------------------------------------------------------------------ tome_match
+def tome_bound(a, b):
+    """(s, ds) [B, Na, Nb]: the cosine similarity of every src row a_i with every dst row b_j."""
+    a, b = f64(a), f64(b)
+    C = a.shape[-1]
+    na, nb = a.norm(dim=-1, keepdim=True), b.norm(dim=-1, keepdim=True)
+    ia = torch.where(na > 0, 1 / na.clamp_min(1e-300), torch.zeros_like(na))
+    ib = torch.where(nb > 0, 1 / nb.clamp_min(1e-300), torch.zeros_like(nb))
+    s = (a * ia) @ (b * ib).transpose(-1, -2)
+    mag = (a.abs() * ia) @ (b.abs() * ib).transpose(-1, -2)
+    return s, C_ACC * (C + 2) * E * mag + 2 * RSQRT_REL * s.abs()
+
+
+def assert_tome(vmax, imax, a, b, what):
+    """vmax within max_j ds of max_j s; the chosen dst within 2 ds of the best; of bit-identical dst rows the lower
+    index. Returns max |vmax - max_j s| / max_j ds."""
+    s, ds = tome_bound(a, b)
+    best, dmax = s.amax(-1), ds.amax(-1)
+    vmax, imax = f64(vmax), imax.long()
+    assert bool(torch.isfinite(vmax).all()), f"{what}: non-finite vmax"
+    assert bool(((imax >= 0) & (imax < s.shape[-1])).all()), f"{what}: index out of range"
+    ratio = ((vmax - best).abs() / dmax.clamp_min(1e-300)).max().item()
+    print(f"BOUND {what}: max |vmax - max_j s| / max_j ds {ratio:.3f}")
+    assert ratio <= 1, f"{what}: vmax over tol, worst {ratio:.3f} x tol"
+    picked = torch.gather(s, -1, imax[..., None])[..., 0]
+    assert bool((picked >= best - 2 * dmax).all()), f"{what}: a chosen dst row is over tol below the best"
+    bb = b.reshape(b.shape[0], b.shape[1], -1)
+    for bt in range(bb.shape[0]):
+        same = (bb[bt][:, None, :] == bb[bt][None, :, :]).all(-1).tril(-1)       # same[j, l]: row l < j is row j
+        first = torch.where(same.any(-1), same.double().argmax(-1), torch.arange(same.shape[0], device=same.device))
+        assert bool((first[imax[bt]] == imax[bt]).all()), f"{what}: a tie went to the higher index"
+    return ratio
+
+
+# ------------------------------------------------------------------------------------------------ shared test inputs
+UPFIRDN_KERNELS = {"3x5": (3, 5), "1x4": (1, 4), "4x1": (4, 1)}
+# (up_x, up_y), (down_x, down_y), (px0, px1, py0, py1)
+UPFIRDN_CFGS = [((2, 1), (1, 2), (2, 1, 0, 3)), ((1, 2), (2, 1), (-1, 2, 1, -1)), ((2, 2), (1, 2), (-1, 2, 1, -1)),
+                ((2, 2), (2, 1), (2, 1, 0, 3))]
+FBA_SHAPES = [(37, 24), (2, 24, 5), (3, 24, 11, 7), (2, 6, 2, 3, 5)]
+SMR_ROWS, SMR_COLS = [1, 5, 257], [1, 63, 64, 65, 200]
+TOME_SHAPES = [(2, 1, 1, 8), (3, 65, 37, 40), (1, 130, 64, 72), (2, 64, 129, 320)]
+
+
+def upfirdn_kernel(kh, kw):
+    """Distinct values, no symmetry: 1, 2, 3 ... with the odd taps at -0.5, scaled to |sum| 1."""
+    k = torch.arange(1.0, kh * kw + 1).reshape(kh, kw)
+    k[..., 1::2] *= -0.5
+    return k / k.abs().sum()
+
+
+def smr_inputs(rows, cols, dtype, device="cpu", seed=0):
+    """8 randn with one +30 spike per row, at a column that moves with the row (the last one in row 0)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(rows, cols, generator=g) * 8
+    x[torch.arange(rows), (cols - 1 - torch.arange(rows) * 7) % cols] += 30
+    return x.to(dtype).to(device)
+
+
+def tome_inputs(B, Na, Nb, C, dtype, device="cpu", seed=0):
+    """a, b as column slices of wider tensors (row stride C + 24); dst rows 0 and Nb - 1 bit-identical and the best
+    match of src row 0, which is a multiple of them; the last src row all zero (where Na > 1)."""
+    g = torch.Generator().manual_seed(seed)
+    wa = torch.randn(B, Na, C + 24, generator=g).to(dtype)
+    wb = torch.randn(B, Nb, C + 24, generator=g).to(dtype)
+    if Nb > 1:
+        wb[:, -1] = wb[:, 0]
+    if Na > 1:
+        wa[:, 0] = wb[:, 0] * 2
+        wa[:, -1] = 0
+    wa, wb = wa.to(device), wb.to(device)
+    return wa[:, :, 8:8 + C], wb[:, :, 8:8 + C]

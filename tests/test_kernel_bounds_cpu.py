@@ -3,16 +3,23 @@ bf16 round; for attention a 64-key-tile online softmax with bf16 P) stays inside
 each of a set of injected faults -- every one of them under the 1e-2 (attention 2e-2) Frobenius-norm threshold
 of the older kernel tests -- is rejected by assert_within. The norm, depthwise and softmax2 bounds are checked in
 bf16 and fp16 against emulations of the kernels' own algorithms (shifted block sums and Chan merges for GroupNorm,
-two passes for LayerNorm)."""
+two passes for LayerNorm). The GRN family and the planar image-space kernels (upfirdn2d, fused_bias_act, resize,
+softmax_rows, tome_match) follow at the end: an emulation of each kernel's own slice, merge and tap structure, and
+the faults its older tests could not see."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from _bounds import (affine_layernorm_bound, assert_within, attention_bound, conv_bound, dwconv_bound, geglu_bound,
-                     gemm_bound, groupnorm_apply_bound, groupnorm_bound, groupnorm_stats_bound, layernorm_bound,
-                     layernorm_stats_bound, lnfold_bound, rel, rs_from_partials_bound, softmax2_bound)
+from _bounds import (FBA_SHAPES, GRN_GNS_SHAPES, GRN_V2_SHAPES, RESIZE_CASES, RESIZE_MODES, SMR_COLS, SMR_ROWS,
+                     TOME_SHAPES, UPFIRDN_CFGS, UPFIRDN_KERNELS, affine_layernorm_bound, assert_tome,
+                     assert_within, attention_bound, conv_bound, dwconv_bound, fused_bias_act_bound, geglu_bound,
+                     gemm_bound, grn_apply_bound, grn_bound, grn_depth, grn_inputs, grn_nx, grn_row_tiled,
+                     grn_scale_weight_bound, grn_slices, grn_stats_bound, groupnorm_apply_bound, groupnorm_bound,
+                     groupnorm_stats_bound, layernorm_bound, layernorm_stats_bound, lnfold_bound, rel, resize_bound,
+                     resize_coords, rs_from_partials_bound, smr_inputs, softmax2_bound, softmax_rows_bound, tome_inputs,
+                     upfirdn2d_bound, upfirdn_kernel)
 
 BF = torch.bfloat16
 DTYPES = [torch.bfloat16, torch.float16]
@@ -568,3 +575,454 @@ def test_softmax2_fault_normaliser_tail_dropped():
     y = _emulate_sm2(x, drop=4)
     assert rel(y, ref) < 1e-2
     _rejected(y, ref, tol, "softmax2: the last 4 columns missing from the normaliser")
+
+
+# ------------------------------------------------------------------------------------------------ GRN
+ALL_DTYPES = [torch.float32, torch.bfloat16, torch.float16]
+GELU_C = (-2.301121339e+00, -1.067757240e-01, 1.014263055e-03)        # kGeluC0 .. 2 (csrc/kernels/common.h)
+
+
+def _gelu_sig(x):
+    """gelu_sig2 in fp32: x * rcp(1 + exp2(xc * q(xc^2))), xc = x clamped to +-8."""
+    xc = x.clamp(-8.0, 8.0)
+    x2 = xc * xc
+    q = (x2 * GELU_C[2] + GELU_C[1]) * x2 + GELU_C[0]
+    return x * (1.0 / (torch.exp2(xc * q) + 1.0))
+
+
+def _grn_parts(x, N, HW, C):
+    """fp32 block sums of squares over 64 rows, as the GELU GEMM's epilogue leaves them: [N, HW / 64, C]."""
+    return x.float().pow(2).reshape(N, HW // 64, 64, C).sum(2)
+
+
+def _emulate_grn(x, gamma, beta, pre_gelu, fault=None, part=None):
+    """cgs_grn_nhwc_v2 in fp32: per slice, four row groups each adding every fourth row, merged as a tree; the
+    finalize loop over S / 4 groups of four slices; sqrt; block sums of 256 channels; inv = 1 / (sum / C + 1e-6);
+    y = beta + a * (1 + gamma * (gx * inv)). part: the GNS form, four chains over the given partials. Faults: 'nx1',
+    'inv0' image 0's inv for all, 'row' the last row of the last slice dropped, 'bsum' the last block sum dropped,
+    'gns' the last partial dropped, 'gelu_stats' the GELU in the apply pass only. Returns (y, gx, bsum)."""
+    N, HW, C = x.shape
+    xf = x.float()
+    a = _gelu_sig(xf) if pre_gelu else xf
+    st = xf if fault == "gelu_stats" else a
+    if part is None:
+        S = grn_slices(N, HW, C)
+        rp = (HW + S - 1) // S
+        parts = []
+        for sl in range(S):
+            r0, r1 = sl * rp, min(HW, sl * rp + rp)
+            if fault == "row" and r1 == HW and r0 < r1:
+                r1 -= 1
+            rg = []
+            for g in range(4):
+                acc = torch.zeros(N, C)
+                for r in range(r0 + g, r1, 4):
+                    acc = acc + st[:, r] * st[:, r]
+                rg.append(acc)
+            parts.append((rg[0] + rg[1]) + (rg[2] + rg[3]))
+        ss = torch.zeros(N, C)
+        for q in range(S // 4):
+            ss = ss + ((parts[4 * q] + parts[4 * q + 1]) + (parts[4 * q + 2] + parts[4 * q + 3]))
+    else:
+        nbk = part.shape[1] - (1 if fault == "gns" else 0)
+        ch = [torch.zeros(N, C) for _ in range(4)]
+        b = 0
+        while b + 4 <= nbk:
+            for j in range(4):
+                ch[j] = ch[j] + part[:, b + j]
+            b += 4
+        for bb in range(b, nbk):
+            ch[0] = ch[0] + part[:, bb]
+        ss = (ch[0] + ch[1]) + (ch[2] + ch[3])
+    gx = ss.sqrt()
+    nblk = (C + 255) // 256
+    bsum = torch.stack([gx[:, i * 256:(i + 1) * 256].sum(1) for i in range(nblk)], 1)
+    used = bsum[:, :-1] if fault == "bsum" else bsum
+    inv = 1.0 / (used.sum(1) / C + 1e-6)
+    if fault == "inv0":
+        inv = inv[:1].expand(N)
+    nx = torch.ones(N, C) if fault == "nx1" else gx * inv[:, None]
+    y = beta.float() + a * (1.0 + gamma.float() * nx)[:, None, :]
+    return y.to(x.dtype), gx, bsum
+
+
+def test_grn_tables_name_the_form_that_runs():
+    """grn_slices and the row-tiled predicate at the table's shapes; nx of the structured input spans [0, 5]."""
+    assert _gelu_sig(torch.zeros(3)).abs().max().item() == 0.0
+    assert {k: grn_slices(*k) for k in GRN_V2_SHAPES} == {(1, 1, 8): 4, (5, 35, 264): 4, (64, 17, 72): 4,
+                                                         (3, 33, 2056): 4, (2, 17, 2048): 4, (2, 16, 1640): 4,
+                                                         (2, 33, 3688): 4, (1, 70, 1632): 8}
+    assert grn_slices(4, 4096, 1536) == 44 and grn_slices(2, 576, 8192) == 16
+    for (N, HW, C), form in GRN_V2_SHAPES.items():
+        assert ("rows" if grn_row_tiled(HW, C) else "grid") == form, (N, HW, C)
+        assert not grn_row_tiled(HW, C, rows=0)
+    assert not grn_row_tiled(35, 2056)           # the case test_grn_apply_row_tiled_matches_grid_stride cannot tell
+    for N, HW, C in list(GRN_V2_SHAPES) + GRN_GNS_SHAPES + [(65, 17, 72), (3, 35, 264)]:
+        for dtype in DTYPES:
+            x, gamma, beta, (cz, cn) = grn_inputs(N, HW, C, dtype)
+            for pre_gelu in (False, True):
+                nx = grn_nx(x, pre_gelu)
+                assert nx.min().item() == 0.0 and nx.max().item() >= 5.0, (N, HW, C, dtype, pre_gelu, nx.max())
+            assert bool((x[:, :, cz] == 0).all()) and x[:, :, cn].max().item() <= -6.0
+            if N > 1:
+                inv = 1 / (x.double().pow(2).sum(1).sqrt().mean(1) + 1e-6)
+                assert (inv.max() / inv.min()).item() > 20
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("pre_gelu", [False, True])
+@pytest.mark.parametrize("N,HW,C", list(GRN_V2_SHAPES))
+def test_grn_emulation_within_bound(N, HW, C, pre_gelu, dtype):
+    x, gamma, beta, _ = grn_inputs(N, HW, C, dtype)
+    y, gx, bsum = _emulate_grn(x, gamma, beta, pre_gelu)
+    what = f"emulated grn {N}x{HW}x{C} gelu={pre_gelu} {dtype}"
+    depth = grn_depth("v2", N, HW, C)
+    ref, tol = grn_bound(x, gamma, beta, pre_gelu, depth)
+    assert_within(y, ref, tol, what)
+    gref, gtol, iref, itol = grn_stats_bound(x, pre_gelu, depth)
+    assert_within(gx, gref, gtol, what + " gx")
+    assert_within(1 / (bsum.double().sum(1) / C + 1e-6), iref, itol, what + " inv")
+    ref, tol = grn_apply_bound(x, gamma, beta, gx, bsum, pre_gelu)
+    assert_within(y, ref, tol, what + " apply")
+    if not pre_gelu:                                  # the atomics of v1 in any order: the looser depth holds too
+        ref, tol = grn_bound(x, gamma, beta, False, grn_depth("v1", N, HW, C))
+        assert_within(y, ref, tol, what + " at the depth of v1")
+    # the exact rounding of the reference uses the store term almost in full and no more
+    ref, tol = grn_bound(x, gamma, beta, pre_gelu, depth)
+    worst = assert_within(ref.to(dtype), ref, tol, what + " rounded reference")
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("N,HW,C", GRN_GNS_SHAPES)
+def test_grn_gns_emulation_and_scale_weight(N, HW, C):
+    x, gamma, beta, _ = grn_inputs(N, HW, C, BF)
+    part = _grn_parts(x, N, HW, C)
+    y, gx, bsum = _emulate_grn(x, gamma, beta, False, part=part)
+    depth = grn_depth("gns", N, HW, C)
+    gref, gtol, iref, itol = grn_stats_bound(None, False, depth, part=part)
+    assert_within(gx, gref, gtol, f"emulated grn gns {N}x{HW}x{C} gx")
+    assert_within(1 / (bsum.double().sum(1) / C + 1e-6), iref, itol, f"emulated grn gns {N}x{HW}x{C} inv")
+    ref, tol = grn_apply_bound(x, gamma, beta, gx, bsum)
+    assert_within(y, ref, tol, f"emulated grn gns {N}x{HW}x{C} apply")
+    # against x itself the torch block sums add 64 + 1 roundings in unknown order to the depth
+    gref, gtol, _, _ = grn_stats_bound(x, False, (depth[0] + 65, depth[1]))
+    assert_within(gx, gref, gtol, f"emulated grn gns {N}x{HW}x{C} gx against x")
+    bad = _emulate_grn(x, gamma, beta, False, fault="gns", part=part)
+    gref, gtol, iref, itol = grn_stats_bound(None, False, depth, part=part)
+    _rejected(bad[1], gref, gtol, f"grn gns {N}x{HW}x{C}: last partial dropped, gx")
+    ref, tol = grn_bound(x, gamma, beta, False, (depth[0] + 65, depth[1]))
+    assert_within(y, ref, tol, f"emulated grn gns {N}x{HW}x{C} against x")
+    _rejected(bad[0], ref, tol, f"grn gns {N}x{HW}x{C}: last partial dropped, y")
+    # the weight-folding consumer
+    O = 24
+    W = torch.randn(O, C, generator=torch.Generator().manual_seed(1)).to(BF)
+    inv = 1.0 / (bsum.sum(1) / C + 1e-6)
+    Wn = (W.float()[None] * (1.0 + gamma.float()[None, None] * gx[:, None] * inv[:, None, None])).to(BF)
+    ref, tol = grn_scale_weight_bound(W, gamma, gx, 1 / (bsum.double().sum(1) / C + 1e-6))
+    assert_within(Wn, ref, tol, f"emulated grn_scale_weight {N}x{O}x{C}")
+    Wn[1:] = (W.float()[None] * (1.0 + gamma.float()[None, None] * gx[1:, None] * inv[:1, None, None])).to(BF)
+    _rejected(Wn, ref, tol, f"grn_scale_weight {N}x{O}x{C}: image 0's normaliser for all")
+
+
+# fault -> (iid shape at which the old check accepts it, structured shape at which the bound rejects it)
+GRN_FAULTS = {"nx1": ((2, 4096, 264), (5, 35, 264)), "inv0": ((3, 1024, 264), (5, 35, 264)),
+              "row": ((3, 1024, 264), (5, 35, 264)), "bsum": ((2, 256, 1544), (5, 35, 264)),
+              "gns": ((2, 1024, 264), (5, 320, 264)), "gelu_stats": ((2, 4096, 264), (5, 35, 264))}
+
+
+@pytest.mark.parametrize("fault", list(GRN_FAULTS))
+def test_grn_faults(fault):
+    """Each fault is under the Frobenius threshold of the older tests on their iid inputs and rejected on the
+    structured ones."""
+    pre_gelu = fault == "gelu_stats"
+    (N, HW, C), small = GRN_FAULTS[fault]
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(N, HW, C, generator=g).to(BF)
+    gamma, beta = (torch.randn(C, generator=g) * 0.5).to(BF), (torch.randn(C, generator=g) * 0.1).to(BF)
+    part = _grn_parts(x, N, HW, C) if fault == "gns" else None
+    y = _emulate_grn(x, gamma, beta, pre_gelu, fault=fault, part=part)[0]
+    xd = F.gelu(x.double()) if pre_gelu else x.double()
+    ref = beta.double() + xd * (1 + gamma.double() * grn_nx(x, pre_gelu))[:, None, :]
+    old = rel(y, ref)
+    print(f"grn fault {fault}: Frobenius rel {old:.2e} on iid {N}x{HW}x{C}")
+    assert old < 1e-2
+    N, HW, C = small
+    for dtype in DTYPES:
+        x, gamma, beta, _ = grn_inputs(N, HW, C, dtype)
+        part = _grn_parts(x, N, HW, C) if fault == "gns" else None
+        L, Lm = grn_depth("gns" if part is not None else "v2", N, HW, C)
+        ref, tol = grn_bound(x, gamma, beta, pre_gelu, (L + 65 if part is not None else L, Lm))
+        y, gx, bsum = _emulate_grn(x, gamma, beta, pre_gelu, part=part)
+        assert_within(y, ref, tol, f"emulated grn {N}x{HW}x{C} {dtype}")
+        y, gx, bsum = _emulate_grn(x, gamma, beta, pre_gelu, fault=fault, part=part)
+        _rejected(y, ref, tol, f"grn {N}x{HW}x{C} {dtype}: fault {fault}")
+        if fault in ("nx1", "inv0"):                  # faults of the apply pass: the statistics it was given are right
+            ref, tol = grn_apply_bound(x, gamma, beta, gx, bsum, pre_gelu)
+            _rejected(y, ref, tol, f"grn apply {N}x{HW}x{C} {dtype}: fault {fault}")
+        if fault in ("row", "gelu_stats"):
+            gref, gtol, _, _ = grn_stats_bound(x, pre_gelu, (L, Lm))
+            _rejected(gx, gref, gtol, f"grn gx {N}x{HW}x{C} {dtype}: fault {fault}")
+
+
+def _no_effect(bad, good):
+    """A fault that cannot show in this configuration: the same values up to fp32 rounding."""
+    return (bad.double() - good.double()).abs().max().item() <= 1e-5 * good.double().abs().max().item()
+
+
+# ------------------------------------------------------------------------------------------------ upfirdn2d
+def _emulate_upfirdn(x, k, up, down, pad, fault=None):
+    """The gather form of upfirdn2d_kernel in fp32. Faults: 'noflip', 'kt' the tap row stride kh instead of kw,
+    'pad' px0 / py0 swapped, 'up' up_x / up_y swapped."""
+    (ux, uy), (dx, dy), (px0, px1, py0, py1) = up, down, pad
+    N, C, H, W = x.shape
+    kh, kw = k.shape
+    Ho, Wo = (H * uy + py0 + py1 - kh) // dy + 1, (W * ux + px0 + px1 - kw) // dx + 1
+    if fault == "pad":
+        px0, py0 = py0, px0
+    if fault == "up":
+        ux, uy = uy, ux
+    xf, taps = x.float(), k.float().reshape(-1)
+    oy, ox = torch.arange(Ho)[:, None], torch.arange(Wo)[None, :]
+    acc = torch.zeros(N, C, Ho, Wo)
+    for i in range(kh):
+        vy = oy * dy + i - py0
+        for j in range(kw):
+            vx = ox * dx + j - px0
+            ok = (vy >= 0) & (vy % uy == 0) & (vy // uy < H) & (vx >= 0) & (vx % ux == 0) & (vx // ux < W)
+            iy, ix = (vy // uy).clamp(0, H - 1).expand(Ho, Wo), (vx // ux).clamp(0, W - 1).expand(Ho, Wo)
+            t = i * kw + j if fault == "noflip" else (kh - 1 - i) * (kh if fault == "kt" else kw) + (kw - 1 - j)
+            acc = acc + torch.where(ok, xf[:, :, iy, ix], torch.zeros(())) * taps[t]
+    return acc.to(x.dtype)
+
+
+@pytest.mark.parametrize("dtype", ALL_DTYPES)
+@pytest.mark.parametrize("kname", list(UPFIRDN_KERNELS))
+def test_upfirdn2d_emulation_and_faults(kname, dtype):
+    x = torch.randn(2, 3, 9, 6, generator=torch.Generator().manual_seed(0)).to(dtype)
+    k = upfirdn_kernel(*UPFIRDN_KERNELS[kname])
+    seen = set()
+    for up, down, pad in UPFIRDN_CFGS:
+        ref, tol = upfirdn2d_bound(x, k, up, down, pad)
+        what = f"upfirdn2d {kname} up={up} down={down} pad={pad} {dtype}"
+        assert_within(_emulate_upfirdn(x, k, up, down, pad), ref, tol, "emulated " + what)
+        for fault in ("noflip", "kt", "pad", "up"):
+            if ((fault == "kt" and 1 in k.shape)     # a 1 x n or n x 1 kernel: the row stride never matters
+                    or (fault == "pad" and pad[0] == pad[2]) or (fault == "up" and up[0] == up[1])):
+                continue
+            bad = _emulate_upfirdn(x, k, up, down, pad, fault)
+            if _no_effect(bad, _emulate_upfirdn(x, k, up, down, pad)):
+                continue                              # up 2, down 2 and an odd pad under a 1-row kernel: all zero
+            _rejected(bad, ref, tol, what + f": fault {fault}")
+            seen.add(fault)
+    assert seen >= ({"noflip", "pad", "up"} | ({"kt"} if kname == "3x5" else set()))
+
+
+# ------------------------------------------------------------------------------------------------ fused_bias_act
+@pytest.mark.parametrize("dtype", ALL_DTYPES)
+@pytest.mark.parametrize("shape", FBA_SHAPES)
+def test_fused_bias_act_emulation_and_fault(shape, dtype):
+    g = torch.Generator().manual_seed(0)
+    x, b = torch.randn(*shape, generator=g).to(dtype), torch.randn(shape[1], generator=g).to(dtype)
+    C, inner = shape[1], math.prod(shape[2:])
+    for slope in (0.2, 0.0):
+        for bias in (b, None):
+            ref, tol = fused_bias_act_bound(x, bias, slope, 2 ** 0.5)
+            i = torch.arange(x.numel())
+            for fault in (False, True):
+                v = x.float().reshape(-1)
+                if bias is not None:
+                    v = v + bias.float()[(i % C) if fault else (i // inner) % C]
+                y = (torch.where(v >= 0, v, v * torch.tensor(slope)) * torch.tensor(2 ** 0.5)).to(dtype).reshape(shape)
+                what = f"fused_bias_act {shape} slope={slope} bias={bias is not None} {dtype}"
+                if not fault:
+                    assert_within(y, ref, tol, "emulated " + what)
+                elif bias is not None and inner > 1:
+                    _rejected(y, ref, tol, what + ": bias index i % C")
+
+
+# ------------------------------------------------------------------------------------------------ resize
+def _emulate_resize(x, size, mode, align, fault=None):
+    """resize_kernel in fp32. Faults: 'nohalf' bilinear without the half-pixel offset, 'noclamp' bicubic taps
+    outside the image read as 0 instead of the border pixel, 'floor' the area window's end floored."""
+    N, C, H, W = x.shape
+    Ho, Wo = size
+    xf = x.float()
+    f32 = lambda v: torch.tensor(float(v), dtype=torch.float32)
+    interp = mode in ("bilinear", "bicubic")
+
+    def scale(n_in, n_out):
+        if align and interp:
+            return f32(n_in - 1) / f32(n_out - 1) if n_out > 1 else f32(0)
+        return f32(n_in) / f32(n_out)
+
+    oy, ox, sh, sw = torch.arange(Ho).float(), torch.arange(Wo).float(), scale(H, Ho), scale(W, Wo)
+    if not interp and mode != "area":
+        off = 0.5 if mode == "nearest-exact" else 0.0
+        iy = torch.floor((oy + off) * sh).long().clamp_max(H - 1)
+        ix = torch.floor((ox + off) * sw).long().clamp_max(W - 1)
+        return xf[:, :, iy][:, :, :, ix].to(x.dtype)
+    if mode == "bilinear":
+        half = not align and fault != "nohalf"
+        fy = ((oy + 0.5) * sh - 0.5).clamp_min(0) if half else oy * sh
+        fx = ((ox + 0.5) * sw - 0.5).clamp_min(0) if half else ox * sw
+        y0, x0 = fy.long().clamp_max(H - 1), fx.long().clamp_max(W - 1)
+        y1, x1 = y0 + (y0 < H - 1), x0 + (x0 < W - 1)
+        ly, lx = (fy - y0)[:, None], fx - x0
+        px = lambda yy, xx: xf[:, :, yy][:, :, :, xx]
+        v = (1 - ly) * ((1 - lx) * px(y0, x0) + lx * px(y0, x1)) + ly * ((1 - lx) * px(y1, x0) + lx * px(y1, x1))
+        return v.to(x.dtype)
+    if mode == "bicubic":
+        A = -0.75
+        c1 = lambda t: ((A + 2) * t - (A + 3)) * t * t + 1
+        c2 = lambda t: ((A * t - 5 * A) * t + 8 * A) * t - 4 * A
+        fy = oy * sh if align else (oy + 0.5) * sh - 0.5
+        fx = ox * sw if align else (ox + 0.5) * sw - 0.5
+        iy, ix = torch.floor(fy), torch.floor(fx)
+        ty, tx = fy - iy, fx - ix
+        wy, wx = [c2(ty + 1), c1(ty), c1(1 - ty), c2(2 - ty)], [c2(tx + 1), c1(tx), c1(1 - tx), c2(2 - tx)]
+        v = torch.zeros(N, C, Ho, Wo)
+        for a in range(4):
+            yy = iy.long() - 1 + a
+            row = torch.zeros(N, C, Ho, Wo)
+            for b in range(4):
+                xx = ix.long() - 1 + b
+                p = xf[:, :, yy.clamp(0, H - 1)][:, :, :, xx.clamp(0, W - 1)]
+                if fault == "noclamp":
+                    inside = ((yy >= 0) & (yy < H))[:, None] & ((xx >= 0) & (xx < W))[None, :]
+                    p = torch.where(inside, p, torch.zeros(()))
+                row = row + wx[b] * p
+            v = v + wy[a][:, None] * row
+        return v.to(x.dtype)
+    v = torch.zeros(N, C, Ho, Wo)
+    for o in range(Ho):
+        y0, y1 = o * H // Ho, -((-(o + 1) * H) // Ho)
+        if fault == "floor":
+            y1 = max((o + 1) * H // Ho, y0 + 1)
+        for q in range(Wo):
+            x0, x1 = q * W // Wo, -((-(q + 1) * W) // Wo)
+            if fault == "floor":
+                x1 = max((q + 1) * W // Wo, x0 + 1)
+            s = torch.zeros(N, C)
+            for yy in range(y0, y1):
+                for xx in range(x0, x1):
+                    s = s + xf[:, :, yy, xx]
+            v[:, :, o, q] = s / f32((y1 - y0) * (x1 - x0))
+    return v.to(x.dtype)
+
+
+def test_resize_sizes_have_no_floor_ambiguity():
+    """No source coordinate of the listed sizes lies within 1e-4 of an integer unless it is exactly one, and those
+    that are floor to it in fp32 as well."""
+    from fractions import Fraction
+    import numpy as np
+    for (_, _, H, W), (Ho, Wo) in RESIZE_CASES:
+        for n_in, n_out in ((H, Ho), (W, Wo)):
+            for mode, align in RESIZE_MODES:
+                if mode == "area":
+                    continue
+                c = resize_coords(n_in, n_out, mode, bool(align))
+                for o in range(n_out):
+                    if align and mode in ("bilinear", "bicubic"):
+                        ex = Fraction(o) * (Fraction(n_in - 1, n_out - 1) if n_out > 1 else 0)
+                        sc = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(0)
+                        f = np.float32(o) * sc
+                    else:
+                        off = Fraction(0) if mode == "nearest" else Fraction(1, 2)
+                        ex = (o + off) * Fraction(n_in, n_out) - (0 if mode.startswith("nearest") else Fraction(1, 2))
+                        f = (np.float32(o) + np.float32(float(off))) * (np.float32(n_in) / np.float32(n_out))
+                        f = f if mode.startswith("nearest") else f - np.float32(0.5)
+                    assert abs(float(ex) - c[o].item()) < 1e-12
+                    if ex.denominator == 1:
+                        if mode.startswith("nearest"):
+                            assert int(np.floor(f)) == int(ex), (n_in, n_out, mode, o, f)
+                    else:
+                        assert abs(ex - round(ex)) >= Fraction(1, 10000), (n_in, n_out, mode, align, o)
+
+
+def _resize_x(shape, dtype):
+    return (torch.randn(*shape, generator=torch.Generator().manual_seed(0)) * 2 + 0.5).to(dtype)
+
+
+@pytest.mark.parametrize("dtype", ALL_DTYPES)
+@pytest.mark.parametrize("mode,align", RESIZE_MODES)
+def test_resize_emulation_within_bound(mode, align, dtype):
+    for shape, size in RESIZE_CASES:
+        x = _resize_x(shape, dtype)
+        ref, tol = resize_bound(x, size, mode, align)
+        y = _emulate_resize(x, size, mode, align)
+        assert_within(y, ref, tol, f"emulated resize {mode} align={align} {shape}->{size} {dtype}")
+        if mode.startswith("nearest"):
+            assert bool((tol == 0).all())
+        else:                                     # the fp64 weights are those of F.interpolate
+            kw = {"align_corners": align} if align is not None else {}
+            want = F.interpolate(x.double(), size=size, mode=mode, **kw)
+            assert (ref - want).abs().max().item() < 1e-9
+
+
+@pytest.mark.parametrize("dtype", ALL_DTYPES)
+@pytest.mark.parametrize("mode,fault", [("bilinear", "nohalf"), ("bicubic", "noclamp"), ("area", "floor")])
+def test_resize_faults(mode, fault, dtype):
+    align = None if mode == "area" else False
+    hit = 0
+    for shape, size in RESIZE_CASES:
+        x = _resize_x(shape, dtype)
+        ref, tol = resize_bound(x, size, mode, align)
+        y = _emulate_resize(x, size, mode, align, fault)
+        if _no_effect(y, _emulate_resize(x, size, mode, align)):
+            continue                              # e.g. the same size: no offset, no border tap, no partial window
+        _rejected(y, ref, tol, f"resize {mode} {shape}->{size} {dtype}: fault {fault}")
+        hit += 1
+    assert hit >= 4
+
+
+# ------------------------------------------------------------------------------------------------ softmax_rows
+def _emulate_smr(x, scale, tail=True):
+    s = x.float() * scale
+    n = s.shape[-1] if tail else 64 * (s.shape[-1] // 64)
+    mx = s[:, :n].amax(-1, keepdim=True)
+    p = torch.exp(s - mx)
+    return p * (1.0 / p[:, :n].sum(-1, keepdim=True))
+
+
+@pytest.mark.parametrize("dtype", ALL_DTYPES)
+@pytest.mark.parametrize("cols", SMR_COLS)
+def test_softmax_rows_emulation_and_fault(cols, dtype):
+    for rows in SMR_ROWS:
+        for scale in (0.125, 1.0):
+            x = smr_inputs(rows, cols, dtype)
+            ref, tol = softmax_rows_bound(x, scale)
+            what = f"softmax_rows {rows}x{cols} scale={scale} {dtype}"
+            assert_within(_emulate_smr(x, scale), ref, tol, "emulated " + what)
+            if cols > 64 and cols % 64:
+                _rejected(_emulate_smr(x, scale, tail=False), ref, tol, what + ": lane tail ignored")
+
+
+# ------------------------------------------------------------------------------------------------ tome_match
+def _emulate_tome(a, b, k_tail=True, high_tie=False):
+    C = a.shape[-1] if k_tail else 32 * (a.shape[-1] // 32)
+    af, bf = a.float(), b.float()
+    inv = lambda t: torch.where(t.pow(2).sum(-1) > 0, torch.rsqrt(t.pow(2).sum(-1)), torch.zeros(()))
+    s = (af[..., :C] @ bf[..., :C].transpose(-1, -2)) * inv(af)[..., :, None] * inv(bf)[..., None, :]
+    v = s.amax(-1)
+    hit = s == v[..., None]
+    n = s.shape[-1]
+    idx = (n - 1 - hit.flip(-1).double().argmax(-1)) if high_tie else hit.double().argmax(-1)
+    return v, idx
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("B,Na,Nb,C", TOME_SHAPES)
+def test_tome_emulation_and_faults(B, Na, Nb, C, dtype):
+    a, b = tome_inputs(B, Na, Nb, C, dtype)
+    assert a.stride(1) == C + 24 and b.stride(1) == C + 24
+    what = f"tome_match {B}x{Na}x{Nb}x{C} {dtype}"
+    v, idx = _emulate_tome(a, b)
+    assert_tome(v, idx, a, b, "emulated " + what)
+    if Na > 1:
+        assert bool((v[:, -1] == 0).all()) and bool((idx[:, 0] == 0).all())
+    if C % 32:
+        with pytest.raises(AssertionError, match="over tol"):
+            assert_tome(*_emulate_tome(a, b, k_tail=False), a, b, what + ": k tail ignored")
+    if Nb > 1:
+        with pytest.raises(AssertionError, match="higher index"):
+            assert_tome(*_emulate_tome(a, b, high_tie=True), a, b, what + ": ties to the higher index")
