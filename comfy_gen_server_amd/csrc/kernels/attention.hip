@@ -961,15 +961,6 @@ CGS_EXPORT int cgs_transpose_bf16(const void* x, void* y, int rows, int cols, lo
 
 static int g_attn_variant = 0;   // 0 auto, 1 generic kernel, 2 D=64 fast kernel (256-row Q blocks), 3 short-KV
                                  // kernel, 4 D=64 r2, 5 D=64 fast kernel with 128-row Q blocks
-static int num_cus_attn() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 256;
-  }
-  return n;
-}
 CGS_EXPORT void cgs_attn_set_variant(int v) { g_attn_variant = v; }
 // s_setprio(1) around the P.V MFMAs of the D = 64 kernel (default on: +1.5 / +2.2 % at SDXL levels 1 / 2,
 // profiles/r03/attn_setprio_pv.log); cgs_attn_set_prio(0) selects the 8-wave form without it (A/B)
@@ -997,7 +988,7 @@ static int flash_attn_impl(const void* q, const void* k, const void* v, void* o,
     static const int qi_env = getenv("CGS_SKV_QI") ? atoi(getenv("CGS_SKV_QI")) : 0;
     int qi = 1;
     if (qi_env == 1 || qi_env == 2 || qi_env == 4) qi = qi_env;
-    else if (Sq >= 2048 && blocks128 / 4 >= 2 * num_cus_attn()) qi = 4;
+    else if (Sq >= 2048 && blocks128 / 4 >= 2 * num_cus()) qi = 4;
     const int nqb3 = (Sq + 128 * qi - 1) / (128 * qi);
     const long long nwg3 = (long long)nqb3 * B * H;
     if (nwg3 > 0x7fffffff) return (int)hipErrorInvalidValue;
@@ -1041,7 +1032,7 @@ static int flash_attn_impl(const void* q, const void* k, const void* v, void* o,
     // 256-row Q blocks (8 waves) unless that leaves the grid under one round of the CUs and the
     // 128-row form (4 waves, two WGs per CU) is asked for (variant 5) or auto-picked (variant 0)
     const long long nwg256 = (long long)((Sq + 255) / 256) * B * H;
-    const bool small = g_attn_variant == 5 || (g_attn_variant == 0 && nwg256 < num_cus_attn());
+    const bool small = g_attn_variant == 5 || (g_attn_variant == 0 && nwg256 < num_cus());
     const int rows = small ? 128 : 256;
     int nqb2 = (Sq + rows - 1) / rows;
     long long nwg2 = (long long)nqb2 * B * H;
@@ -1188,7 +1179,7 @@ CGS_EXPORT int cgs_flash_attn_fwd_kv2(const void* q, const void* k1, const void*
   // 128-row blocks only for tiny grids: at Cascade batch 1 (B x H = 64 / 40, 576 / 1024 queries: 192 / 160
   // workgroups of 256 rows) the 256-row form measured 13-16 % faster than the 128-row one it used to pick
   // below one round of CUs (profiles/r05/attn_kv2_rows.md)
-  const bool small = g_kv2_rows == 128 || (g_kv2_rows == 0 && nwg256 * 4 < num_cus_attn());
+  const bool small = g_kv2_rows == 128 || (g_kv2_rows == 0 && nwg256 * 4 < num_cus());
   const int rows = small ? 128 : 256;
   const int nqb2 = (Sq + rows - 1) / rows;
   const long long nwg2 = (long long)nqb2 * B * H;

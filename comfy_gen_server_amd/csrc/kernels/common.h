@@ -20,6 +20,17 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 enum CgsDType { CGS_F32 = 0, CGS_BF16 = 1, CGS_F16 = 2 };
 
+// Compute units of the current device (256 when the query fails), asked once per process: the grid size of the
+// persistent kernels and the under-filled-grid thresholds of the launchers.
+inline int num_cus() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    (void)hipGetDevice(&dev);
+    return hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
+  }();
+  return n;
+}
+
 __device__ __forceinline__ float bf2f(u16 v) {
   return __uint_as_float(((uint32_t)v) << 16);
 }

@@ -760,16 +760,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                                                           a.group_m);
 }
 
-static int conv_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 int v6_conv_ds();   // gemm.hip: v6 DMA placement for convs (CGS_V6_CONV_DS / cgs_v6_set_mode)
 
 template <int LD, int DS, bool GNS = false, int NJ = 5, int PFE = CGS_CONV_PFE>
@@ -791,7 +781,7 @@ static void conv_v6w4_go(ConvArgs& a, hipStream_t stream) {
   const int M = a.N * a.Ho * a.Wo;
   a.tiles_n = (a.Cout + Gm::BN - 1) / Gm::BN;
   const long long T = (long long)((M + Gm::BM - 1) / Gm::BM) * a.tiles_n;
-  const int grid = (int)(T < 2 * conv_num_cus() ? T : 2 * conv_num_cus());
+  const int grid = (int)(T < 2 * num_cus() ? T : 2 * num_cus());
   int ld = conv_fast_ok(a) ? (conv_kd(a) ? 2 : 1) : ((a.flags & CONV_UP2X) && conv_kd(a) ? 3 : 0);
   if (g_conv_v6_ld >= 0 && g_conv_v6_ld < ld) ld = ld == 3 ? 0 : g_conv_v6_ld;
   if (ld) conv_magic(a);
@@ -817,7 +807,7 @@ static void conv_v6_go(ConvArgs& a, hipStream_t stream, bool n128 = false) {
   const int bn = n128 ? pq::Geo<4>::BN : pq::BN;
   a.tiles_n = (a.Cout + bn - 1) / bn;
   const long long T = (long long)((M + pq::BM - 1) / pq::BM) * a.tiles_n;
-  const int grid = (int)(T < conv_num_cus() ? T : conv_num_cus());
+  const int grid = (int)(T < num_cus() ? T : num_cus());
   const int ds = v6_conv_ds();
   int ld = conv_fast_ok(a) ? (conv_kd(a) ? 2 : 1) : ((a.flags & CONV_UP2X) && conv_kd(a) ? 3 : 0);
   if (g_conv_v6_ld >= 0 && g_conv_v6_ld < ld) ld = ld == 3 ? 0 : g_conv_v6_ld;
@@ -881,8 +871,8 @@ static void conv_v7_go(ConvArgs& a, hipStream_t stream, void* ws = nullptr, long
   const long long T = (long long)((M + ppk::BM - 1) / ppk::BM) * a.tiles_n;
   a.sp = ppk::Split{0, 1, nullptr, nullptr, 0};
   long long U = T;
-  if (ws && ws_bytes >= ppk::split_ws_bytes(T, K / ppk::BK, conv_num_cus())) {
-    a.sp.S = ppk::split_plan(T, K / ppk::BK, conv_num_cus(), a.sp.t_full);
+  if (ws && ws_bytes >= ppk::split_ws_bytes(T, K / ppk::BK, num_cus())) {
+    a.sp.S = ppk::split_plan(T, K / ppk::BK, num_cus(), a.sp.t_full);
     if (a.sp.S > 1) {
       const long long tail = T - a.sp.t_full;
       a.sp.part = (float4*)ws;
@@ -892,7 +882,7 @@ static void conv_v7_go(ConvArgs& a, hipStream_t stream, void* ws = nullptr, long
       else U = a.sp.t_full + tail * a.sp.S;
     }
   }
-  const int grid = (int)(U < conv_num_cus() ? U : conv_num_cus());
+  const int grid = (int)(U < num_cus() ? U : num_cus());
   if (conv_fast_ok(a) && !conv_wide(a)) {
     conv_magic(a);
     a.img_rsrc = 0;

@@ -16,6 +16,7 @@
 #include "mfma_pp.h"
 #include "mfma_pp160.h"
 #include "mfma_ppk.h"
+#include "gemm_args.h"
 
 #define G_BM 128
 #define G_BN 128
@@ -337,32 +338,15 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_nt_v2_kernel(
 static int g_tile_group = 4;   // grouped tile order (tile rows per group; 1 = row-major): 4 measured -0.3 % per headline job vs 8 (profiles/r05/tile_group_ab.json)
 CGS_EXPORT void cgs_set_tile_group(int g) { g_tile_group = g < 1 ? 1 : g; }
 
-static int gemm_v2_launch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                          long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                          hipStream_t stream) {
-  const bool wide = N >= 1024;
+static int gemm_v2_launch(const GemmArgs& a) {
+  const bool wide = a.N >= 1024;
   const int BN = wide ? 256 : 128;
-  int tiles_m = (M + 255) / 256;
-  int tiles_n = (N + BN - 1) / BN;
+  int tiles_m = (a.M + 255) / 256;
+  int tiles_n = (a.N + BN - 1) / BN;
   long long nwg = (long long)tiles_m * tiles_n;
-  size_t lds = 2 * (256 * 64 * 2 + BN * 64 * 2);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_bf16_nt_v2_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        2 * (256 * 64 * 2 + 256 * 64 * 2));
-    hipFuncSetAttribute((const void*)gemm_bf16_nt_v2_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        2 * (256 * 64 * 2 + 128 * 64 * 2));
-    attr_set = true;
-  }
-  if (wide) {
-    gemm_bf16_nt_v2_kernel<256><<<(unsigned)nwg, 512, lds, stream>>>(
-        (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi,
-        alpha, tiles_n, g_tile_group);
-  } else {
-    gemm_bf16_nt_v2_kernel<128><<<(unsigned)nwg, 512, lds, stream>>>(
-        (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi,
-        alpha, tiles_n, g_tile_group);
-  }
+  const int lds = 2 * (256 * 64 * 2 + BN * 64 * 2);
+  if (wide) launch_gemm<gemm_bf16_nt_v2_kernel<256>>((unsigned)nwg, 512, lds, a, tiles_n, g_tile_group);
+  else launch_gemm<gemm_bf16_nt_v2_kernel<128>>((unsigned)nwg, 512, lds, a, tiles_n, g_tile_group);
   return (int)hipGetLastError();
 }
 
@@ -416,41 +400,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 template <int BN, int BMV, int NS = mc::STAGES>
-static int gemm_small_tile_launch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
-                                  int K, long long lda, long long ldw, long long ldc, long long ldr, int epi,
-                                  float alpha, hipStream_t stream, const float* rs, const float* cs) {
-  using Cf = mc::Cfg<BN, 4, BMV, NS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v8_kernel<BN, BMV, NS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              Cf::LDS);
-    attr_set = true;
-  }
-  const int tiles_n = (N + BN - 1) / BN;
-  const long long nwg = (long long)((M + BMV - 1) / BMV) * tiles_n;
+static int gemm_small_tile_launch(const GemmArgs& a) {
+  const int tiles_n = (a.N + BN - 1) / BN;
+  const long long nwg = (long long)((a.M + BMV - 1) / BMV) * tiles_n;
   if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  gemm_bf16_nt_v8_kernel<BN, BMV, NS><<<(unsigned)nwg, 256, Cf::LDS, stream>>>(
-      (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-      tiles_n, g_tile_group, rs, cs);
+  launch_gemm<gemm_bf16_nt_v8_kernel<BN, BMV, NS>>((unsigned)nwg, 256, mc::Cfg<BN, 4, BMV, NS>::LDS, a, tiles_n,
+                                                   g_tile_group, a.rs, a.cs);
   return (int)hipGetLastError();
 }
 
 // variant 8 = 128 x 128, 10 = 64 x 128, 11 = 128 x 64 (4-stage ring); 12 = 64 x 128 and 13 = 128 x 64 with
 // a 6-stage ring (72 / 72 KiB: still two workgroups per CU), 14 = 128 x 128 with 5 stages (80 KiB)
-static int gemm_v8_launch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                          long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                          hipStream_t stream, int variant = 8, const float* rs = nullptr, const float* cs = nullptr) {
-  if (variant == 10)
-    return gemm_small_tile_launch<128, 64>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, rs, cs);
-  if (variant == 11)
-    return gemm_small_tile_launch<64, 128>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, rs, cs);
-  if (variant == 12)
-    return gemm_small_tile_launch<128, 64, 6>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, rs, cs);
-  if (variant == 13)
-    return gemm_small_tile_launch<64, 128, 6>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, rs, cs);
-  if (variant == 14)
-    return gemm_small_tile_launch<128, 128, 5>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, rs, cs);
-  return gemm_small_tile_launch<128, 128>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, rs, cs);
+static int gemm_v8_launch(const GemmArgs& a, int variant = kVariantV8) {
+  if (variant == kVariantT64x128) return gemm_small_tile_launch<128, 64>(a);
+  if (variant == kVariantT128x64) return gemm_small_tile_launch<64, 128>(a);
+  if (variant == kVariantT64x128s6) return gemm_small_tile_launch<128, 64, 6>(a);
+  if (variant == kVariantT128x64s6) return gemm_small_tile_launch<64, 128, 6>(a);
+  if (variant == kVariantT128s5) return gemm_small_tile_launch<128, 128, 5>(a);
+  return gemm_small_tile_launch<128, 128>(a);
 }
 
 // Split-K form of the v8 family (K13, batch-1 grids): blockIdx.y = K slice z, the tile computes
@@ -522,21 +489,16 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
+// S K-slices of Ks columns each into the fp32 partials a.ws
 template <int BN, int BMV, int NS = mc::STAGES>
-static int gemm_splitk_go(const void* A, const void* W, float* ws, int M, int N, int Ks, int S, long long lda,
-                          long long ldw, hipStream_t stream) {
+static int gemm_splitk_go(const GemmArgs& a, int Ks, int S) {
   using Cf = mc::Cfg<BN, 4, BMV, NS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v8sk_kernel<BN, BMV, NS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS);
-    attr_set = true;
-  }
-  const int tiles_n = (N + BN - 1) / BN;
-  const long long nwg = (long long)((M + BMV - 1) / BMV) * tiles_n;
+  max_dynamic_lds_once<gemm_bf16_nt_v8sk_kernel<BN, BMV, NS>>(Cf::LDS);
+  const int tiles_n = (a.N + BN - 1) / BN;
+  const long long nwg = (long long)((a.M + BMV - 1) / BMV) * tiles_n;
   if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  gemm_bf16_nt_v8sk_kernel<BN, BMV, NS><<<dim3((unsigned)nwg, (unsigned)S), 256, Cf::LDS, stream>>>(
-      (const u16*)A, (const u16*)W, ws, M, N, Ks, lda, ldw, tiles_n, g_tile_group);
+  gemm_bf16_nt_v8sk_kernel<BN, BMV, NS><<<dim3((unsigned)nwg, (unsigned)S), 256, Cf::LDS, a.stream>>>(
+      (const u16*)a.A, (const u16*)a.W, (float*)a.ws, a.M, a.N, Ks, a.lda, a.ldw, tiles_n, g_tile_group);
   return (int)hipGetLastError();
 }
 
@@ -556,13 +518,14 @@ CGS_EXPORT int cgs_gemm_bf16_splitk(const void* A, const void* W, void* C, const
       ws_bytes < cgs_splitk_ws_bytes(M, N, splits) ||
       (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)R | (uintptr_t)ws) & 15))
     return (int)hipErrorInvalidValue;
+  const GemmArgs a{A, W, C, bias, R, rs, cs, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, ws, ws_bytes};
   const int Ks = K / splits;
   int rc;
   switch (variant) {
-    case 10: rc = gemm_splitk_go<128, 64>(A, W, ws, M, N, Ks, splits, lda, ldw, stream); break;
-    case 11: rc = gemm_splitk_go<64, 128>(A, W, ws, M, N, Ks, splits, lda, ldw, stream); break;
-    case 14: rc = gemm_splitk_go<128, 128, 5>(A, W, ws, M, N, Ks, splits, lda, ldw, stream); break;
-    default: rc = gemm_splitk_go<128, 128>(A, W, ws, M, N, Ks, splits, lda, ldw, stream);
+    case kVariantT64x128: rc = gemm_splitk_go<128, 64>(a, Ks, splits); break;
+    case kVariantT128x64: rc = gemm_splitk_go<64, 128>(a, Ks, splits); break;
+    case kVariantT128s5: rc = gemm_splitk_go<128, 128, 5>(a, Ks, splits); break;
+    default: rc = gemm_splitk_go<128, 128>(a, Ks, splits);
   }
   if (rc) return rc;
   const long long chunks = (long long)M * (N / 8);
@@ -578,32 +541,20 @@ CGS_EXPORT int cgs_gemm_bf16_splitk(const void* A, const void* W, void* C, const
 }
 
 template <int BN, int NW>
-static void gemm_v3_go(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                       long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                       hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v3_kernel<BN, NW>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, mc::Cfg<BN, NW>::LDS);
-    attr_set = true;
-  }
-  const int tiles_n = (N + BN - 1) / BN;
-  const long long nwg = (long long)((M + mc::BM - 1) / mc::BM) * tiles_n;
-  gemm_bf16_nt_v3_kernel<BN, NW><<<(unsigned)nwg, 64 * NW, mc::Cfg<BN, NW>::LDS, stream>>>(
-      (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-      tiles_n, g_tile_group);
+static void gemm_v3_go(const GemmArgs& a) {
+  const int tiles_n = (a.N + BN - 1) / BN;
+  const long long nwg = (long long)((a.M + mc::BM - 1) / mc::BM) * tiles_n;
+  launch_gemm<gemm_bf16_nt_v3_kernel<BN, NW>>((unsigned)nwg, 64 * NW, mc::Cfg<BN, NW>::LDS, a, tiles_n, g_tile_group);
 }
 
-static int gemm_v3_launch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                          long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha, int nw,
-                          hipStream_t stream) {
-  const int BN = mc::pick_bn(M, N);
+static int gemm_v3_launch(const GemmArgs& a, int nw) {
+  const int BN = mc::pick_bn(a.M, a.N);
   if (nw == 8) {
-    if (BN == 256) gemm_v3_go<256, 8>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
-    else gemm_v3_go<128, 8>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
+    if (BN == 256) gemm_v3_go<256, 8>(a);
+    else gemm_v3_go<128, 8>(a);
   } else {
-    if (BN == 256) gemm_v3_go<256, 4>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
-    else gemm_v3_go<128, 4>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
+    if (BN == 256) gemm_v3_go<256, 4>(a);
+    else gemm_v3_go<128, 4>(a);
   }
   return (int)hipGetLastError();
 }
@@ -635,20 +586,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   pp::tile(al, W, ldw, M, N, K, tm * pp::BM, tn * pp::BN, e, smem);
 }
 
-static int gemm_v5_launch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                          long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                          hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              pp::LDS);
-    attr_set = true;
-  }
-  const int tiles_n = (N + pp::BN - 1) / pp::BN;
-  const long long nwg = (long long)((M + pp::BM - 1) / pp::BM) * tiles_n;
-  gemm_bf16_nt_v5_kernel<<<(unsigned)nwg, pp::THREADS, pp::LDS, stream>>>(
-      (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-      tiles_n, g_tile_group);
+static int gemm_v5_launch(const GemmArgs& a) {
+  const int tiles_n = (a.N + pp::BN - 1) / pp::BN;
+  const long long nwg = (long long)((a.M + pp::BM - 1) / pp::BM) * tiles_n;
+  launch_gemm<gemm_bf16_nt_v5_kernel>((unsigned)nwg, pp::THREADS, pp::LDS, a, tiles_n, g_tile_group);
   return (int)hipGetLastError();
 }
 
@@ -734,16 +675,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   pq::run<DenseA8, LN, 1, false, false, false, RSO, 1, 5, 2, 4>(al, W, ldw, M, N, K, e, smem, tiles_m, tiles_n,
                                                                  group_m);
 }
-static int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 // v6 DMA placement (pq::run DS): CGS_V6_DS at first use, cgs_v6_set_mode() after (in-process A/B).
 // Default 1 (A parts in phase 0, B parts in phase 1): +4..11 % over all-in-phase-0 on the SDXL
 // N = 640 / 1280 GEMMs and +2..4 % on the Cout = 320 convs (profiles/r03/v6_dma_split.log).
@@ -762,112 +693,74 @@ int v6_conv_ds() {
 }
 CGS_EXPORT void cgs_v6_set_mode(int m) { g_v6_ds = m; g_v6_conv_ds = m; }
 
+// (a.rs / a.cs: the LayerNorm-fold operands; a.part: the RSO statistics partials)
 template <bool LN, int DS, bool GG = false, int ACT = 0, bool RSO = false, int NI = 4>
-static void gemm_v6_go(int grid, const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
-                       int K, long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                       int tiles_m, int tiles_n, hipStream_t stream, const float* rs, const float* cs,
-                       float* rso = nullptr) {
-  constexpr int lds = pq::Geo<5, NI>::LDS;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v6_kernel<LN, DS, GG, ACT, RSO, NI>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  gemm_bf16_nt_v6_kernel<LN, DS, GG, ACT, RSO, NI><<<grid, pq::THREADS, lds, stream>>>(
-      (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-      tiles_m, tiles_n, g_tile_group, rs, cs, rso);
+static void gemm_v6_go(const GemmArgs& a) {
+  const int tiles_n = (a.N + pq::BN - 1) / pq::BN;
+  const int tiles_m = (a.M + 64 * NI - 1) / (64 * NI);
+  const long long T = (long long)tiles_m * tiles_n;
+  const int grid = (int)(T < num_cus() ? T : num_cus());
+  launch_gemm<gemm_bf16_nt_v6_kernel<LN, DS, GG, ACT, RSO, NI>>(grid, pq::THREADS, pq::Geo<5, NI>::LDS, a, tiles_m,
+                                                                tiles_n, g_tile_group, a.rs, a.cs, a.part);
 }
 
 template <bool LN, bool RSO>
-static int gemm_v6w4_go(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                        long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                        hipStream_t stream, const float* rs, const float* cs, float* rso) {
+static int gemm_v6w4_go(const GemmArgs& a) {
   using Gm = pq::Geo<5, 2, 4>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v6w4_kernel<LN, RSO>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, Gm::LDS);
-    attr_set = true;
-  }
-  const int tiles_n = (N + Gm::BN - 1) / Gm::BN;
-  const int tiles_m = (M + Gm::BM - 1) / Gm::BM;
+  const int tiles_n = (a.N + Gm::BN - 1) / Gm::BN;
+  const int tiles_m = (a.M + Gm::BM - 1) / Gm::BM;
   const long long T = (long long)tiles_m * tiles_n;
   const int grid = (int)(T < 2 * num_cus() ? T : 2 * num_cus());
-  gemm_bf16_nt_v6w4_kernel<LN, RSO><<<grid, 256, Gm::LDS, stream>>>(
-      (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-      tiles_m, tiles_n, g_tile_group, rs, cs, rso);
+  launch_gemm<gemm_bf16_nt_v6w4_kernel<LN, RSO>>(grid, 256, Gm::LDS, a, tiles_m, tiles_n, g_tile_group, a.rs, a.cs,
+                                                 a.part);
   return (int)hipGetLastError();
 }
 
-static int gemm_v6_launch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                          long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                          hipStream_t stream, const float* rs = nullptr, const float* cs = nullptr, int ni = 4) {
+// ni: 16-row MFMA blocks per wave -- 4 (variant 6), 2 (variant 19), 1 (variant 20: the one-wave-group kernel)
+static int gemm_v6_launch(const GemmArgs& a, int ni = 4) {
+  const int epi = a.epi;
   if (ni == 1) {   // variant 20: 128 x 80 tiles, one wave group (plain / bias / residual or LayerNorm-folded)
     if (epi & (EPI_GELU | EPI_GEGLU)) return (int)hipErrorInvalidValue;
-    if (epi & EPI_LNFOLD)
-      return gemm_v6w4_go<true, false>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, rs, cs,
-                                       nullptr);
-    return gemm_v6w4_go<false, false>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, rs, cs,
-                                      nullptr);
+    if (epi & EPI_LNFOLD) return gemm_v6w4_go<true, false>(a);
+    return gemm_v6w4_go<false, false>(a);
   }
-  const int tiles_n = (N + pq::BN - 1) / pq::BN;
-  const int tiles_m = (M + 64 * ni - 1) / (64 * ni);
-  const long long T = (long long)tiles_m * tiles_n;
-  const int grid = (int)(T < num_cus() ? T : num_cus());
   if (ni == 2) {   // 128 x 160 tiles (variant 19): plain / bias / residual or LayerNorm-folded, default DMA split
     if (epi & (EPI_GELU | EPI_GEGLU)) return (int)hipErrorInvalidValue;
-    if (epi & EPI_LNFOLD)
-      gemm_v6_go<true, 1, false, false, false, 2>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-                                                  tiles_m, tiles_n, stream, rs, cs);
-    else
-      gemm_v6_go<false, 1, false, false, false, 2>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-                                                   tiles_m, tiles_n, stream, rs, cs);
+    if (epi & EPI_LNFOLD) gemm_v6_go<true, 1, false, false, false, 2>(a);
+    else gemm_v6_go<false, 1, false, false, false, 2>(a);
     return (int)hipGetLastError();
   }
   int ds = v6_ds();
-  if ((long long)M * lda * 2 >= (1ll << 31)) ds &= ~64;    // buffer-descriptor forms need < 2 GiB operands
-  if ((long long)N * ldw * 2 >= (1ll << 31)) ds &= ~128;
+  if ((long long)a.M * a.lda * 2 >= (1ll << 31)) ds &= ~64;    // buffer-descriptor forms need < 2 GiB operands
+  if ((long long)a.N * a.ldw * 2 >= (1ll << 31)) ds &= ~128;
   if (epi & EPI_GELU) {    // GELU epilogue: plain or LayerNorm-folded form (no GEGLU)
     if (epi & EPI_GEGLU) return (int)hipErrorInvalidValue;
     if (epi_act_code(epi) > CGS_ACT_GELU) {   // another activation of the set: its family's kernel, no LN fold
       if (epi & EPI_LNFOLD) return (int)hipErrorInvalidValue;
-      if (epi_act_code(epi) >= CGS_ACT_RELU)
-        gemm_v6_go<false, 1, false, ACT_FAM_LIN>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-                                                 tiles_m, tiles_n, stream, rs, cs);
-      else
-        gemm_v6_go<false, 1, false, ACT_FAM_SIG>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-                                                 tiles_m, tiles_n, stream, rs, cs);
+      if (epi_act_code(epi) >= CGS_ACT_RELU) gemm_v6_go<false, 1, false, ACT_FAM_LIN>(a);
+      else gemm_v6_go<false, 1, false, ACT_FAM_SIG>(a);
       return (int)hipGetLastError();
     }
-    if (epi & EPI_LNFOLD)
-      gemm_v6_go<true, 1, false, true>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m,
-                                       tiles_n, stream, rs, cs);
-    else
-      gemm_v6_go<false, 1, false, true>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m,
-                                        tiles_n, stream, rs, cs);
+    if (epi & EPI_LNFOLD) gemm_v6_go<true, 1, false, true>(a);
+    else gemm_v6_go<false, 1, false, true>(a);
     return (int)hipGetLastError();
   }
   if (epi & EPI_GEGLU) {   // GEGLU epilogue (pq::run GG): split-DMA main loop, N % 160 == 0 (host-checked)
-    if (epi & EPI_LNFOLD)
-      gemm_v6_go<true, 1, true>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n,
-                                stream, rs, cs);
-    else
-      gemm_v6_go<false, 1, true>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n,
-                                 stream, rs, cs);
+    if (epi & EPI_LNFOLD) gemm_v6_go<true, 1, true>(a);
+    else gemm_v6_go<false, 1, true>(a);
     return (int)hipGetLastError();
   }
   auto go = [&](auto lnc) {
     constexpr bool L = decltype(lnc)::value;
     switch (ds) {
-      case 0: gemm_v6_go<L, 0>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n, stream, rs, cs); break;
-      case 3: gemm_v6_go<L, 3>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n, stream, rs, cs); break;
-      case 17: gemm_v6_go<L, 17>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n, stream, rs, cs); break;
-      case 19: gemm_v6_go<L, 19>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n, stream, rs, cs); break;
-      case 65: gemm_v6_go<L, 65>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n, stream, rs, cs); break;
-      case 129: gemm_v6_go<L, 129>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n, stream, rs, cs); break;
-      case 193: gemm_v6_go<L, 193>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n, stream, rs, cs); break;
-      default: gemm_v6_go<L, 1>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m, tiles_n, stream, rs, cs);
+      case 0: gemm_v6_go<L, 0>(a); break;
+      case 3: gemm_v6_go<L, 3>(a); break;
+      case 17: gemm_v6_go<L, 17>(a); break;
+      case 19: gemm_v6_go<L, 19>(a); break;
+      case 65: gemm_v6_go<L, 65>(a); break;
+      case 129: gemm_v6_go<L, 129>(a); break;
+      case 193: gemm_v6_go<L, 193>(a); break;
+      default: gemm_v6_go<L, 1>(a);
     }
   };
   if (epi & EPI_LNFOLD) go(std::true_type{});
@@ -907,64 +800,47 @@ CGS_EXPORT int cgs_gemm_bf16_gelu_gns(const void* A, const void* W, void* C, con
   const int tiles_n = (N + pq::BN - 1) / pq::BN, tiles_m = (M + pq::BM - 1) / pq::BM;
   const long long T = (long long)tiles_m * tiles_n;
   const int grid = (int)(T < num_cus() ? T : num_cus());
-  static bool attr[2] = {false, false};
-  const bool ln = (epi & EPI_LNFOLD) != 0;
-  if (!attr[ln]) {
-    (void)hipFuncSetAttribute(ln ? (const void*)gemm_bf16_nt_v6_gns_kernel<true> : (const void*)gemm_bf16_nt_v6_gns_kernel<false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, pq::LDS);
-    attr[ln] = true;
-  }
-  if (ln)
+  if (epi & EPI_LNFOLD) {
+    max_dynamic_lds_once<gemm_bf16_nt_v6_gns_kernel<true>>(pq::LDS);
     gemm_bf16_nt_v6_gns_kernel<true><<<grid, pq::THREADS, pq::LDS, stream>>>(
         (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, M, N, K, lda, ldw, ldc, epi, tiles_m, tiles_n,
         g_tile_group, rs, cs, part, hw);
-  else
+  } else {
+    max_dynamic_lds_once<gemm_bf16_nt_v6_gns_kernel<false>>(pq::LDS);
     gemm_bf16_nt_v6_gns_kernel<false><<<grid, pq::THREADS, pq::LDS, stream>>>(
         (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, M, N, K, lda, ldw, ldc, epi, tiles_m, tiles_n,
         g_tile_group, rs, cs, part, hw);
+  }
   return (int)hipGetLastError();
 }
 
 // v6 GEMM (bias / residual epilogue) that also writes per-row LayerNorm statistics partials of its output
 // (pq::run RSO): part = [M][N / 80] (mean, M2) float pairs; cgs_ln_rs_from_partials turns them into the
 // (mean, rstd) rows a LayerNorm-folded GEMM reads. N % 160 == 0, K % 64 == 0, K >= 128.
-static int gemm_rowstats(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                         long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha, float* part,
-                         int ni, hipStream_t stream);
+static int gemm_rowstats(const GemmArgs& a, int ni) {
+  if (!a.part || a.N % 160 || a.K % 64 || a.K < 128 || (a.epi & ~(EPI_BIAS | EPI_RESIDUAL)) || a.lda % 8 ||
+      a.ldw % 8 || a.ldc % 8 || ((a.epi & EPI_RESIDUAL) && a.ldr % 8) || ((uintptr_t)a.bias % 8) ||
+      ((((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.C | (uintptr_t)a.R)) % 16) || ((uintptr_t)a.part % 8))
+    return (int)hipErrorInvalidValue;
+  if (a.M == 0) return 0;
+  if (ni == 1) return gemm_v6w4_go<false, true>(a);
+  if (ni == 2) gemm_v6_go<false, 1, false, false, true, 2>(a);
+  else gemm_v6_go<false, 1, false, false, true>(a);
+  return (int)hipGetLastError();
+}
 CGS_EXPORT int cgs_gemm_bf16_rowstats(const void* A, const void* W, void* C, const void* bias, const void* R, int M,
                                       int N, int K, long long lda, long long ldw, long long ldc, long long ldr, int epi,
                                       float alpha, float* part, hipStream_t stream) {
-  return gemm_rowstats(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, part, 4, stream);
+  const GemmArgs a{A, W, C, bias, R, nullptr, nullptr, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, nullptr, 0, part};
+  return gemm_rowstats(a, 4);
 }
-// variant 6 (256 x 160) or 19 (128 x 160 tiles)
+// variant 6 (256 x 160), 19 (128 x 160) or 20 (128 x 80 tiles)
 CGS_EXPORT int cgs_gemm_bf16_rowstats_v(const void* A, const void* W, void* C, const void* bias, const void* R, int M,
                                         int N, int K, long long lda, long long ldw, long long ldc, long long ldr,
                                         int epi, float alpha, float* part, int variant, hipStream_t stream) {
-  if (variant != 6 && variant != 19 && variant != 20) return (int)hipErrorInvalidValue;
-  return gemm_rowstats(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, part,
-                       variant == 20 ? 1 : variant == 19 ? 2 : 4, stream);
-}
-static int gemm_rowstats(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                         long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha, float* part,
-                         int ni, hipStream_t stream) {
-  if (!part || N % 160 || K % 64 || K < 128 || (epi & ~(EPI_BIAS | EPI_RESIDUAL)) || lda % 8 || ldw % 8 ||
-      ldc % 8 || ((epi & EPI_RESIDUAL) && ldr % 8) || ((uintptr_t)bias % 8) ||
-      ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)R)) % 16) || ((uintptr_t)part % 8))
-    return (int)hipErrorInvalidValue;
-  if (M == 0) return 0;
-  if (ni == 1) return gemm_v6w4_go<false, true>(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream,
-                                                nullptr, nullptr, part);
-  const int tiles_n = N / pq::BN;
-  const int tiles_m = (M + 64 * ni - 1) / (64 * ni);
-  const long long T = (long long)tiles_m * tiles_n;
-  const int grid = (int)(T < num_cus() ? T : num_cus());
-  if (ni == 2)
-    gemm_v6_go<false, 1, false, false, true, 2>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-                                                tiles_m, tiles_n, stream, nullptr, nullptr, part);
-  else
-    gemm_v6_go<false, 1, false, false, true>(grid, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, tiles_m,
-                                             tiles_n, stream, nullptr, nullptr, part);
-  return (int)hipGetLastError();
+  if (variant != kVariantV6 && variant != kVariantV6m128 && variant != kVariantV6w4) return (int)hipErrorInvalidValue;
+  const GemmArgs a{A, W, C, bias, R, nullptr, nullptr, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, nullptr, 0, part};
+  return gemm_rowstats(a, variant == kVariantV6w4 ? 1 : variant == kVariantV6m128 ? 2 : 4);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -989,39 +865,23 @@ static int v7_dbg() {
 }
 CGS_EXPORT void cgs_v7_set_dbg(int d) { g_v7_dbg = d; }
 
-// ws (may be null): split-K tail workspace of >= cgs_v7_ws_bytes(M, N, K) bytes; without it the
+// a.ws (may be null): split-K tail workspace of >= cgs_v7_ws_bytes(M, N, K) bytes; without it the
 // tail round runs whole tiles.
-static int gemm_v7_launch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                          long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                          void* ws, long long ws_bytes, hipStream_t stream, const float* rs = nullptr,
-                          const float* cs = nullptr) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v7_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ppk::LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v7_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ppk::LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v7_kernel<false, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, ppk::LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v7_kernel<true, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, ppk::LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_v7_kernel<false, false, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, ppk::LDS);
-    attr_set = true;
-  }
+static int gemm_v7_launch(const GemmArgs& a) {
+  const int M = a.M, N = a.N, K = a.K, epi = a.epi;
   const int tiles_n = (N + ppk::BN - 1) / ppk::BN;
   const int tiles_m = (M + ppk::BM - 1) / ppk::BM;
   const long long T = (long long)tiles_m * tiles_n;
   ppk::Split sp{0, 1, nullptr, nullptr, v7_dbg()};
   long long U = T;
-  if (ws && ws_bytes >= ppk::split_ws_bytes(T, K / ppk::BK, num_cus())) {
+  if (a.ws && a.ws_bytes >= ppk::split_ws_bytes(T, K / ppk::BK, num_cus())) {
     sp.S = ppk::split_plan(T, K / ppk::BK, num_cus(), sp.t_full);
     if (sp.S > 1) {
       const long long tail = T - sp.t_full;
-      sp.part = (float4*)ws;
-      sp.cnt = (int*)((char*)ws + tail * sp.S * 32ll * ppk::THREADS * 16);
+      sp.part = (float4*)a.ws;
+      sp.cnt = (int*)((char*)a.ws + tail * sp.S * 32ll * ppk::THREADS * 16);
       if (!(sp.dbg & 2)) {
-        ppk::zero_counters_kernel<<<1, 256, 0, stream>>>(sp.cnt, (int)tail);
+        ppk::zero_counters_kernel<<<1, 256, 0, a.stream>>>(sp.cnt, (int)tail);
         hipError_t err = hipGetLastError();
         if (err != hipSuccess) return (int)err;
       }
@@ -1032,14 +892,11 @@ static int gemm_v7_launch(const void* A, const void* W, void* C, const void* bia
   int grid = (int)(U < num_cus() ? U : num_cus());
   if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
   const bool ln = (epi & EPI_LNFOLD) != 0;
-#define CGS_V7L(GG, LNF)                                                                                            \
-  gemm_bf16_nt_v7_kernel<GG, LNF><<<grid, ppk::THREADS, ppk::LDS, stream>>>(                                        \
-      (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, \
-      tiles_m, tiles_n, g_tile_group, sp, rs, cs)
+#define CGS_V7L(...) \
+  launch_gemm<gemm_bf16_nt_v7_kernel<__VA_ARGS__>>(grid, ppk::THREADS, ppk::LDS, a, tiles_m, tiles_n, g_tile_group, sp, \
+                                                   a.rs, a.cs)
   if (epi & EPI_F32OUT) {
-    gemm_bf16_nt_v7_kernel<false, false, true><<<grid, ppk::THREADS, ppk::LDS, stream>>>(
-        (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-        tiles_m, tiles_n, g_tile_group, sp, rs, cs);
+    CGS_V7L(false, false, true);
   } else if (epi & EPI_GEGLU) {
     if (ln) CGS_V7L(true, true);
     else CGS_V7L(true, false);
@@ -1182,17 +1039,15 @@ CGS_EXPORT long long cgs_gemm_skinny_ws_bytes(int M, int N, int K) {
   return S > 1 ? (long long)S * M * N * 4 : 0;
 }
 
-static int gemm_skinny_launch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
-                              int K, long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                              hipStream_t stream, void* ws = nullptr, long long ws_bytes = 0) {
-  const int S = skinny_splits(M, N, K);
-  const bool split = S > 1 && ws && ws_bytes >= (long long)S * M * N * 4;
+// a.ws (may be null): the K-split workspace of >= cgs_gemm_skinny_ws_bytes(M, N, K) bytes
+static int gemm_skinny_launch(const GemmArgs& a) {
+  const int M = a.M, N = a.N;
+  const int S = skinny_splits(M, N, a.K);
+  const bool split = S > 1 && a.ws && a.ws_bytes >= (long long)S * M * N * 4;
   const dim3 g((unsigned)((N + 15) / 16), split ? (unsigned)S : 1u);
-  float* part = split ? (float*)ws : nullptr;
+  float* part = split ? (float*)a.ws : nullptr;
   const int mr = (M + 15) / 16;
-#define CGS_SKINNY(MRV)                                                                                          \
-  gemm_skinny_kernel<MRV><<<g, 64 * SK_WAVES, 0, stream>>>((const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias,         \
-                                                 (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, part)
+#define CGS_SKINNY(MRV) launch_gemm<gemm_skinny_kernel<MRV>>(g, 64 * SK_WAVES, 0, a, part)
   switch (mr) {
     case 0: CGS_SKINNY(1); break;
     case 2: CGS_SKINNY(2); break;
@@ -1206,8 +1061,8 @@ static int gemm_skinny_launch(const void* A, const void* W, void* C, const void*
 #undef CGS_SKINNY
   if (split) {
     const long long n = (long long)M * N;
-    gemm_skinny_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(
-        part, (u16*)C, (const u16*)bias, (const u16*)R, M, N, S, ldc, ldr, epi, alpha);
+    gemm_skinny_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, a.stream>>>(
+        part, (u16*)a.C, (const u16*)a.bias, (const u16*)a.R, M, N, S, a.ldc, a.ldr, a.epi, a.alpha);
   }
   return (int)hipGetLastError();
 }
@@ -1220,117 +1075,85 @@ CGS_EXPORT int cgs_gemm_skinny_ws(const void* A, const void* W, void* C, const v
       (epi & (EPI_GEGLU | EPI_F32OUT | EPI_LNFOLD | CGS_EPI_ACT_MASK)))   // (the split reduce knows the erf GELU only)
     return (int)hipErrorInvalidValue;
   if (M == 0 || N == 0) return 0;
-  return gemm_skinny_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, ws, ws_bytes);
+  return gemm_skinny_launch(GemmArgs{A, W, C, bias, R, nullptr, nullptr, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
+                                     stream, ws, ws_bytes});
 }
 
 static int g_gemm_variant = -1;   // -1 auto, 1 = v1 only, 2 = v2, 3 = v3 (4 waves), 4 = v3 (8 waves), 5 = v5 ping-pong
 
 CGS_EXPORT void cgs_gemm_set_variant(int v) { g_gemm_variant = v; }
 
-// w6 (gemm_w6.hip): one-wave-per-SIMD 256x256x64 persistent kernel with full-line LDS-DMA; variant 16.
-// variant 17: its 256x160 form (128 x 80 wave tiles).
-CGS_EXPORT int cgs_gemm_w6_ok(int M, int N, int K, long long lda, long long ldw, long long ldc, long long ldr, int epi,
-                              int bn);
-CGS_EXPORT int cgs_gemm_bf16_w6(const void* A, const void* W, void* C, const void* bias, const void* R, const float* rs,
-                                const float* cs, int M, int N, int K, long long lda, long long ldw, long long ldc,
-                                long long ldr, int epi, float alpha, int dbg, int group_m, int grid_cap, int bn,
-                                hipStream_t stream);
-constexpr int kVariantW6 = 16, kVariantW6n160 = 17;
-
-// w6's pointer alignment (cgs_gemm_bf16_w6 returns hipErrorInvalidValue otherwise)
-static bool w6_ptrs_ok(const void* A, const void* W, const void* C, const void* bias, const void* R, int epi) {
-  return ((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 == 0 && (!(epi & EPI_RESIDUAL) || (uintptr_t)R % 16 == 0) &&
-         (!(epi & EPI_BIAS) || (uintptr_t)bias % 16 == 0);
-}
-
-static int gemm_dispatch(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N, int K,
-                         long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
-                         int variant, hipStream_t stream, void* ws = nullptr, long long ws_bytes = 0) {
+// variant: a GemmVariant. w6 (gemm_w6.hip): one-wave-per-SIMD 256x256x64 persistent kernel with full-line LDS-DMA,
+// variant 16; variant 17: its 256x160 form (128 x 80 wave tiles). a.ws: the v7 split-K tail workspace.
+static int gemm_dispatch(const GemmArgs& a, int variant) {
+  const int M = a.M, N = a.N, K = a.K, epi = a.epi;
+  const long long lda = a.lda, ldw = a.ldw;
   if (K % 8 || lda % 8 || ldw % 8) return (int)hipErrorInvalidValue;
   if ((epi & EPI_GEGLU) && (N % 32)) return (int)hipErrorInvalidValue;
   // activation code bits: only beside EPI_GELU, only the codes a GEMM knows (leaky_relu has no parameter here)
   if ((epi & CGS_EPI_ACT_MASK) && (!(epi & EPI_GELU) || epi_act_code(epi) > CGS_ACT_RELU)) return (int)hipErrorInvalidValue;
   if (M == 0 || N == 0) return 0;
+  const bool skinny = M <= 128 && (variant == kVariantAuto || variant == kVariantSkinny);
   if (epi & EPI_GELU) {
     // GELU (or EPI_GELU | code << 8: another activation) epilogue kernels: skinny (M <= 128), v6 (variant 6),
     // the mc::tile family (v3 / v4, v8 and the small tiles; auto = v8). No GEGLU / LayerNorm-fold / fp32-out
     // combination.
     if (epi & (EPI_GEGLU | EPI_LNFOLD | EPI_F32OUT)) return (int)hipErrorInvalidValue;
-    const bool ok = (K % 32 == 0) && (N % 8 == 0) && (ldc % 8 == 0) && (!(epi & EPI_RESIDUAL) || ldr % 8 == 0) &&
-                    ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)R)) % 16 == 0);
+    const bool ok = (K % 32 == 0) && (N % 8 == 0) && (a.ldc % 8 == 0) && (!(epi & EPI_RESIDUAL) || a.ldr % 8 == 0) &&
+                    ((((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.C | (uintptr_t)a.R)) % 16 == 0);
     if (!ok) return (int)hipErrorInvalidValue;
-    if (M <= 128 && (variant == -1 || variant == 9))
-      return gemm_skinny_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
-    if (variant == 6) {
-      if (K % 64 || K < 128 || ((uintptr_t)bias % 8)) return (int)hipErrorInvalidValue;
-      return gemm_v6_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
+    if (skinny) return gemm_skinny_launch(a);
+    if (variant == kVariantV6) {
+      if (K % 64 || K < 128 || ((uintptr_t)a.bias % 8)) return (int)hipErrorInvalidValue;
+      return gemm_v6_launch(a);
     }
-    if (variant == 3 || variant == 4)
-      return gemm_v3_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, variant == 3 ? 4 : 8, stream);
-    if (variant == -1 || variant == 8 || (variant >= 10 && variant <= 14))
-      return gemm_v8_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream,
-                            variant == -1 ? 8 : variant);
+    if (variant == kVariantV3 || variant == kVariantV4) return gemm_v3_launch(a, variant == kVariantV3 ? 4 : 8);
+    if (variant == kVariantAuto || small_tile_variant(variant))
+      return gemm_v8_launch(a, variant == kVariantAuto ? kVariantV8 : variant);
     return (int)hipErrorInvalidValue;
   }
-  // v2 needs K % 64 == 0 and 16-B aligned rows; it pays off once there are >= ~256 big tiles'
-  // worth of work (otherwise the 128x128 kernel keeps more CUs busy).
-  bool v2_ok = (K % 64 == 0) && (lda % 8 == 0) && (ldw % 8 == 0) && M >= 256 && N >= 128 &&
-               (((uintptr_t)A | (uintptr_t)W) % 16 == 0);
-  const int nout = (epi & EPI_GEGLU) ? N / 2 : N;
-  bool v3_ok = (K % 32 == 0) && (lda % 8 == 0) && (ldw % 8 == 0) && (nout % 8 == 0) && (ldc % 8 == 0) &&
-               (!(epi & EPI_RESIDUAL) || ldr % 8 == 0) &&
-               ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)R)) % 16 == 0);
+  const bool v2_ok = a.v2_ok(), v3_ok = a.v3_ok();
+  // the ping-pong loops (v6, v7): whole 64-deep K tiles, at least two, 8-B aligned bias
+  const bool pp_ok = v3_ok && K % 64 == 0 && K >= 128 && ((uintptr_t)a.bias % 8 == 0);
+  // v7's 32-bit operand offsets
+  const bool lt4g = (long long)M * lda * 2 < (1ll << 32) && (long long)N * ldw * 2 < (1ll << 32);
   // skinny M (<= 128 rows): weight-bandwidth bound, one workgroup per 16 columns (variant 9, or auto)
-  if (M <= 128 && K % 32 == 0 && !(epi & (EPI_GEGLU | EPI_F32OUT | EPI_LNFOLD)) && (variant == -1 || variant == 9) &&
-      lda % 8 == 0 && ldw % 8 == 0 && (((uintptr_t)A | (uintptr_t)W) % 16 == 0))
-    return gemm_skinny_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
+  if (skinny && K % 32 == 0 && !(epi & (EPI_GEGLU | EPI_F32OUT | EPI_LNFOLD)) && lda % 8 == 0 && ldw % 8 == 0 &&
+      (((uintptr_t)a.A | (uintptr_t)a.W) % 16 == 0))
+    return gemm_skinny_launch(a);
   if (epi & EPI_F32OUT) {   // fp32 output: v7 only, plain / bias epilogue
-    if ((epi & (EPI_GEGLU | EPI_RESIDUAL | EPI_LNFOLD)) || !v3_ok || K % 64 || K < 128 || ((uintptr_t)bias % 8) ||
-        (long long)M * lda * 2 >= (1ll << 32) || (long long)N * ldw * 2 >= (1ll << 32))
-      return (int)hipErrorInvalidValue;
-    return gemm_v7_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, ws, ws_bytes, stream);
+    if ((epi & (EPI_GEGLU | EPI_RESIDUAL | EPI_LNFOLD)) || !pp_ok || !lt4g) return (int)hipErrorInvalidValue;
+    return gemm_v7_launch(a);
   }
   if (variant == kVariantW6 || variant == kVariantW6n160) {
     // a table choice made by shape: a call outside w6's stride / alignment domain (16-B bias / residual
     // pointers, views with lda != K) runs on the auto path instead of failing
     const int bn = variant == kVariantW6 ? 256 : 160;
-    if (cgs_gemm_w6_ok(M, N, K, lda, ldw, ldc, ldr, epi, bn) && w6_ptrs_ok(A, W, C, bias, R, epi))
-      return cgs_gemm_bf16_w6(A, W, C, bias, R, nullptr, nullptr, M, N, K, lda, ldw, ldc, ldr, epi, alpha, 0, 4, 0,
-                              bn, stream);
-    variant = -1;
+    if (a.w6_ok(bn)) return gemm_w6(a, 0, 4, 0, bn);
+    variant = kVariantAuto;
   }
-  if (v3_ok && K % 64 == 0 && K >= 128 && variant == 6 && (!(epi & EPI_GEGLU) || (N % 160 == 0 && !(epi & EPI_RESIDUAL))) &&
-      ((uintptr_t)bias % 8 == 0))
-    return gemm_v6_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
-  if (v3_ok && K % 64 == 0 && K >= 128 && (variant == 19 || variant == 20) && !(epi & EPI_GEGLU) &&
-      ((uintptr_t)bias % 8 == 0))
-    return gemm_v6_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, nullptr, nullptr,
-                          variant == 20 ? 1 : 2);
-  if (v3_ok && K % 64 == 0 && K >= 128 && variant == 7 && !((epi & EPI_GEGLU) && (epi & EPI_RESIDUAL)) &&
-      ((uintptr_t)bias % 8 == 0) && (long long)M * lda * 2 < (1ll << 32) && (long long)N * ldw * 2 < (1ll << 32))
-    return gemm_v7_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, ws, ws_bytes, stream);
-  if (v3_ok && (variant == 8 || (variant >= 10 && variant <= 14)) && !(epi & EPI_LNFOLD))
-    return gemm_v8_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, variant);
-  if (v3_ok && K % 64 == 0 && variant == 5)
-    return gemm_v5_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
-  if (v3_ok && (variant >= 3 || variant == -1)) {
+  if (pp_ok && variant == kVariantV6 && (!(epi & EPI_GEGLU) || (N % 160 == 0 && !(epi & EPI_RESIDUAL))))
+    return gemm_v6_launch(a);
+  if (pp_ok && (variant == kVariantV6m128 || variant == kVariantV6w4) && !(epi & EPI_GEGLU))
+    return gemm_v6_launch(a, variant == kVariantV6w4 ? 1 : 2);
+  if (pp_ok && variant == kVariantV7 && !((epi & EPI_GEGLU) && (epi & EPI_RESIDUAL)) && lt4g) return gemm_v7_launch(a);
+  if (v3_ok && small_tile_variant(variant) && !(epi & EPI_LNFOLD)) return gemm_v8_launch(a, variant);
+  if (v3_ok && K % 64 == 0 && variant == kVariantV5) return gemm_v5_launch(a);
+  if (v3_ok && (variant >= kVariantV3 || variant == kVariantAuto)) {
     long long t3 = (long long)((M + 255) / 256) * ((N + 127) / 128);
-    if (variant >= 3 || t3 >= 128)
-      return gemm_v3_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-                            variant == 3 ? 4 : 8, stream);
+    if (variant >= kVariantV3 || t3 >= 128) return gemm_v3_launch(a, variant == kVariantV3 ? 4 : 8);
   }
-  if (v2_ok && variant != 1 && variant < 3) {
+  if (v2_ok && variant != kVariantV1 && variant < kVariantV3) {
     const int BN = N >= 1024 ? 256 : 128;
     long long t2 = (long long)((M + 255) / 256) * ((N + BN - 1) / BN);
-    if (variant == 2 || t2 >= 128)
-      return gemm_v2_launch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream);
+    if (variant == kVariantV2 || t2 >= 128) return gemm_v2_launch(a);
   }
   int tiles_m = (M + G_BM - 1) / G_BM;
   int tiles_n = (N + G_BN - 1) / G_BN;
   long long nwg = (long long)tiles_m * tiles_n;
-  gemm_bf16_nt_kernel<false><<<(unsigned)nwg, 256, 0, stream>>>((const u16*)A, W, (u16*)C, (const u16*)bias,
-                                                               (const u16*)R, M, N, K, lda, ldw, ldc, ldr, epi, alpha,
-                                                               tiles_n);
+  gemm_bf16_nt_kernel<false><<<(unsigned)nwg, 256, 0, a.stream>>>((const u16*)a.A, a.W, (u16*)a.C, (const u16*)a.bias,
+                                                                 (const u16*)a.R, M, N, K, lda, ldw, a.ldc, a.ldr, epi,
+                                                                 a.alpha, tiles_n);
   return (int)hipGetLastError();
 }
 
@@ -1351,72 +1174,63 @@ CGS_EXPORT int cgs_gemm_bf16_w8(const void* A, const void* W, void* C, const voi
 CGS_EXPORT int cgs_gemm_bf16(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
                              int K, long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
                              hipStream_t stream) {
-  return gemm_dispatch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, g_gemm_variant, stream);
+  const GemmArgs a{A, W, C, bias, R, nullptr, nullptr, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream};
+  return gemm_dispatch(a, g_gemm_variant);
 }
 
 // Per-call kernel choice (used by the op-layer autotuner): variant as in cgs_gemm_set_variant.
 CGS_EXPORT int cgs_gemm_bf16_v(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
                                int K, long long lda, long long ldw, long long ldc, long long ldr, int epi, float alpha,
                                int variant, hipStream_t stream) {
-  if (variant == -2) variant = g_gemm_variant;   // -2: the process-wide override (default auto)
-  return gemm_dispatch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, variant, stream);
+  if (variant == kVariantProcess) variant = g_gemm_variant;   // -2: the process-wide override (default auto)
+  const GemmArgs a{A, W, C, bias, R, nullptr, nullptr, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream};
+  return gemm_dispatch(a, variant);
 }
 
 // v7 with the split-K tail workspace (ws from the caller's allocator, >= cgs_v7_ws_bytes bytes).
 CGS_EXPORT int cgs_gemm_bf16_v7ws(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
                                   int K, long long lda, long long ldw, long long ldc, long long ldr, int epi,
                                   float alpha, void* ws, long long ws_bytes, hipStream_t stream) {
-  return gemm_dispatch(A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha, 7, stream, ws, ws_bytes);
+  const GemmArgs a{A, W, C, bias, R, nullptr, nullptr, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream, ws, ws_bytes};
+  return gemm_dispatch(a, kVariantV7);
 }
 
 // LayerNorm folded into the GEMM (MC_EPI_LNFOLD): C = rstd_r * (A W'^T - mean_r * cs) + bias, with
 // rs = per-row (mean, rstd) of A (cgs_layernorm_stats) and W' / cs / bias precomputed by the caller
 // (W' = W * gamma, cs = rowsum(W'), bias = b + W beta). v7 only (+ optional GEGLU, split-K tail).
-static int gemm_lnfold(const void* A, const void* W, void* C, const void* bias, const float* rs, const float* cs,
-                       int M, int N, int K, long long lda, long long ldw, long long ldc, int epi, void* ws,
-                       long long ws_bytes, int variant, hipStream_t stream) {
-  const int nout = (epi & EPI_GEGLU) ? N / 2 : N;
+// a: as the two entries below build it (no residual, alpha = 1, EPI_LNFOLD beside the caller's flags).
+static int gemm_lnfold(const GemmArgs& a, int variant) {
+  const int N = a.N, epi = a.epi;
   if (epi & CGS_EPI_ACT_MASK) return (int)hipErrorInvalidValue;   // LN-folded forms: erf GELU only
-  if (!rs || !cs || K % 64 || K < 128 || lda % 8 || ldw % 8 || ldc % 8 || nout % 8 || (epi & EPI_RESIDUAL) ||
-      ((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 || ((uintptr_t)bias % 8) || ((uintptr_t)cs % 16) ||
-      ((uintptr_t)rs % 8) || (long long)M * lda * 2 >= (1ll << 32) || (long long)N * ldw * 2 >= (1ll << 32))
-    return (int)hipErrorInvalidValue;
-  if (M == 0 || N == 0) return 0;
+  if (!a.lnfold_ok()) return (int)hipErrorInvalidValue;
+  if (a.M == 0 || N == 0) return 0;
   if (epi & EPI_GELU) {    // LayerNorm -> Linear -> GELU (Cascade ChannelMLP): v6 ACT or the mc::tile kernels
-    if ((epi & EPI_GEGLU) || variant == 7) return (int)hipErrorInvalidValue;
-    if (variant == 6 || (variant < 0 && N % 160 == 0))
-      return gemm_v6_launch(A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, stream, rs, cs);
-    return gemm_v8_launch(A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, stream,
-                          variant < 0 ? 8 : variant, rs, cs);
+    if ((epi & EPI_GEGLU) || variant == kVariantV7) return (int)hipErrorInvalidValue;
+    if (variant == kVariantV6 || (variant < 0 && N % 160 == 0)) return gemm_v6_launch(a);
+    return gemm_v8_launch(a, variant < 0 ? kVariantV8 : variant);
   }
   if (variant == kVariantW6 || variant == kVariantW6n160) {    // outside w6's domain: the v6 / v7 choice below
     const int bn = variant == kVariantW6 ? 256 : 160;
-    if (cgs_gemm_w6_ok(M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, bn) && w6_ptrs_ok(A, W, C, bias, nullptr, epi))
-      return cgs_gemm_bf16_w6(A, W, C, bias, nullptr, rs, cs, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, 0, 4,
-                              0, bn, stream);
-    variant = -1;
+    if (a.w6_ok(bn)) return gemm_w6(a, 0, 4, 0, bn);
+    variant = kVariantAuto;
   }
   // v6 (256x160) for the N = 640 / 1280 projections (the cross-attention query), v7 otherwise
-  if (variant == 8 || (variant >= 10 && variant <= 14))
-    return gemm_v8_launch(A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, stream, variant,
-                          rs, cs);
+  if (small_tile_variant(variant)) return gemm_v8_launch(a, variant);
   const bool v6_ok = N % 160 == 0;   // incl. GEGLU (pq::run GG)
-  if (variant == 6 && !v6_ok) return (int)hipErrorInvalidValue;
-  if (variant == 19 || variant == 20) {     // 128 x 160 / 128 x 80 tiles: no GEGLU form
-    if (N % 80 || (variant == 19 && !v6_ok) || (epi & EPI_GEGLU)) return (int)hipErrorInvalidValue;
-    return gemm_v6_launch(A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, stream, rs, cs,
-                          variant == 20 ? 1 : 2);
+  if (variant == kVariantV6 && !v6_ok) return (int)hipErrorInvalidValue;
+  if (variant == kVariantV6m128 || variant == kVariantV6w4) {     // 128 x 160 / 128 x 80 tiles: no GEGLU form
+    if (N % 80 || (variant == kVariantV6m128 && !v6_ok) || (epi & EPI_GEGLU)) return (int)hipErrorInvalidValue;
+    return gemm_v6_launch(a, variant == kVariantV6w4 ? 1 : 2);
   }
-  if (variant == 6 || (variant < 0 && v6_ok && !(epi & EPI_GEGLU) && N <= 1280))
-    return gemm_v6_launch(A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, stream, rs, cs);
-  return gemm_v7_launch(A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, ws, ws_bytes, stream,
-                        rs, cs);
+  if (variant == kVariantV6 || (variant < 0 && v6_ok && !(epi & EPI_GEGLU) && N <= 1280)) return gemm_v6_launch(a);
+  return gemm_v7_launch(a);
 }
 
 CGS_EXPORT int cgs_gemm_bf16_lnfold(const void* A, const void* W, void* C, const void* bias, const float* rs,
                                     const float* cs, int M, int N, int K, long long lda, long long ldw, long long ldc,
                                     int epi, void* ws, long long ws_bytes, hipStream_t stream) {
-  return gemm_lnfold(A, W, C, bias, rs, cs, M, N, K, lda, ldw, ldc, epi, ws, ws_bytes, -1, stream);
+  const GemmArgs a{A, W, C, bias, nullptr, rs, cs, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, stream, ws, ws_bytes};
+  return gemm_lnfold(a, kVariantAuto);
 }
 
 // Per-call kernel choice for the LayerNorm-folded GEMM (op-layer autotuner): -1 = v6 / v7 by shape,
@@ -1424,5 +1238,6 @@ CGS_EXPORT int cgs_gemm_bf16_lnfold(const void* A, const void* W, void* C, const
 CGS_EXPORT int cgs_gemm_bf16_lnfold_v(const void* A, const void* W, void* C, const void* bias, const float* rs,
                                       const float* cs, int M, int N, int K, long long lda, long long ldw, long long ldc,
                                       int epi, void* ws, long long ws_bytes, int variant, hipStream_t stream) {
-  return gemm_lnfold(A, W, C, bias, rs, cs, M, N, K, lda, ldw, ldc, epi, ws, ws_bytes, variant, stream);
+  const GemmArgs a{A, W, C, bias, nullptr, rs, cs, M, N, K, lda, ldw, ldc, 0, epi | EPI_LNFOLD, 1.0f, stream, ws, ws_bytes};
+  return gemm_lnfold(a, variant);
 }

@@ -41,6 +41,7 @@
 // Needs K % 128 == 0 (an even number of K-tiles), N % 16 == 0, 16-B aligned rows.
 #include "common.h"
 #include "mfma_core.h"
+#include "gemm_args.h"
 
 namespace w6 {
 
@@ -501,33 +502,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   w6::run<DBG, GG, LN, BN>(A, lda, W, ldw, M, N, K, e, smem, tiles_m, tiles_n, group_m);
 }
 
-static int g_w6_cus = 0;
-
 template <int DBG, bool GG, bool LN, int BN>
-static int launch_w6(const void* A, const void* W, void* C, const void* bias, const void* R, const float* rs,
-                     const float* cs, int M, int N, int K, long long lda, long long ldw, long long ldc, long long ldr,
-                     int epi, float alpha, int group_m, int grid_cap, hipStream_t stream) {
+static int launch_w6(const GemmArgs& a, int group_m, int grid_cap) {
   constexpr int LDS = w6::Geo<BN>::LDS;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_nt_w6_kernel<DBG, GG, LN, BN>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
-  const int tiles_m = (M + w6::BM - 1) / w6::BM, tiles_n = (N + BN - 1) / BN;
+  max_dynamic_lds_once<gemm_bf16_nt_w6_kernel<DBG, GG, LN, BN>>(LDS);
+  const int tiles_m = (a.M + w6::BM - 1) / w6::BM, tiles_n = (a.N + BN - 1) / BN;
   const long long T = (long long)tiles_m * tiles_n;
   if (T > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  if (g_w6_cus <= 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_w6_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_w6_cus <= 0) g_w6_cus = 256;
-  }
-  const int cap = grid_cap > 0 ? grid_cap : g_w6_cus;     // one workgroup per CU
+  const int cap = grid_cap > 0 ? grid_cap : num_cus();     // one workgroup per CU
   const unsigned grid = (unsigned)(T < cap ? T : cap);
-  gemm_bf16_nt_w6_kernel<DBG, GG, LN, BN><<<grid, w6::THREADS, LDS, stream>>>(
-      (const u16*)A, (const u16*)W, (u16*)C, (const u16*)bias, (const u16*)R, rs, cs, M, N, K, lda, ldw, ldc, ldr, epi,
-      alpha, tiles_m, tiles_n, group_m);
+  gemm_bf16_nt_w6_kernel<DBG, GG, LN, BN><<<grid, w6::THREADS, LDS, a.stream>>>(
+      (const u16*)a.A, (const u16*)a.W, (u16*)a.C, (const u16*)a.bias, (const u16*)a.R, a.rs, a.cs, a.M, a.N, a.K,
+      a.lda, a.ldw, a.ldc, a.ldr, a.epi, a.alpha, tiles_m, tiles_n, group_m);
   return (int)hipGetLastError();
 }
 
@@ -544,27 +530,29 @@ CGS_EXPORT int cgs_gemm_w6_ok(int M, int N, int K, long long lda, long long ldw,
   return 1;
 }
 
-// epi: MC_EPI_BIAS / RESIDUAL / GEGLU / LNFOLD (rs: [M][2] (mean, rstd), cs: [N] colsums of W' = W * gamma).
+// a.epi: MC_EPI_BIAS / RESIDUAL / GEGLU / LNFOLD (a.rs: [M][2] (mean, rstd), a.cs: [N] colsums of W' = W * gamma).
 // dbg: ablation probes (results wrong by design for dbg & 3). grid_cap: persistent grid (0 = one workgroup
 // per CU; >= tiles = one tile per workgroup). bn: tile width 256 or 160.
-CGS_EXPORT int cgs_gemm_bf16_w6(const void* A, const void* W, void* C, const void* bias, const void* R, const float* rs,
-                                const float* cs, int M, int N, int K, long long lda, long long ldw, long long ldc,
-                                long long ldr, int epi, float alpha, int dbg, int group_m, int grid_cap, int bn,
-                                hipStream_t stream) {
-  if (!cgs_gemm_w6_ok(M, N, K, lda, ldw, ldc, ldr, epi, bn) || ((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 ||
-      ((epi & MC_EPI_RESIDUAL) && (uintptr_t)R % 16) || ((epi & MC_EPI_BIAS) && (uintptr_t)bias % 16) ||
-      ((epi & MC_EPI_LNFOLD) && (!rs || !cs || (uintptr_t)cs % 16)))
+int gemm_w6(const GemmArgs& a, int dbg, int group_m, int grid_cap, int bn) {
+  const int epi = a.epi;
+  if (!a.w6_ok(bn) || ((epi & MC_EPI_LNFOLD) && (!a.rs || !a.cs || (uintptr_t)a.cs % 16)))
     return (int)hipErrorInvalidValue;
-  if (M == 0 || N == 0) return 0;
+  if (a.M == 0 || a.N == 0) return 0;
   if (group_m <= 0) group_m = 4;
   const bool gg = (epi & MC_EPI_GEGLU) != 0, ln = (epi & MC_EPI_LNFOLD) != 0;
-#define W6_CASE(D, GGV, LNV, BNV)                                                                                 \
-  if (dbg == D && gg == GGV && ln == LNV && bn == BNV)                                                            \
-    return launch_w6<D, GGV, LNV, BNV>(A, W, C, bias, R, rs, cs, M, N, K, lda, ldw, ldc, ldr, epi, alpha, group_m, \
-                                       grid_cap, stream);
+#define W6_CASE(D, GGV, LNV, BNV) \
+  if (dbg == D && gg == GGV && ln == LNV && bn == BNV) return launch_w6<D, GGV, LNV, BNV>(a, group_m, grid_cap);
   W6_CASE(0, false, false, 256) W6_CASE(0, true, false, 256) W6_CASE(0, false, true, 256) W6_CASE(0, true, true, 256)
   W6_CASE(0, false, false, 160) W6_CASE(0, false, true, 160)
   W6_CASE(1, false, false, 256) W6_CASE(2, false, false, 256) W6_CASE(3, false, false, 256)
 #undef W6_CASE
   return (int)hipErrorInvalidValue;
+}
+
+CGS_EXPORT int cgs_gemm_bf16_w6(const void* A, const void* W, void* C, const void* bias, const void* R, const float* rs,
+                                const float* cs, int M, int N, int K, long long lda, long long ldw, long long ldc,
+                                long long ldr, int epi, float alpha, int dbg, int group_m, int grid_cap, int bn,
+                                hipStream_t stream) {
+  const GemmArgs a{A, W, C, bias, R, rs, cs, M, N, K, lda, ldw, ldc, ldr, epi, alpha, stream};
+  return gemm_w6(a, dbg, group_m, grid_cap, bn);
 }

@@ -5,7 +5,9 @@ the one that runs (gemm_dispatch / conv_launch / flash_attn_impl fall through to
 case relies on that). References are fp64 on the device. The shapes are the smallest that reach an edge: a single
 partial tile, one row / one 8-wide vector past a full tile, the minimum K, an odd number of K steps, more tiles
 than a persistent kernel's workgroups, the workspace (split-K) paths. The guard tests place C with ldc = N + 8 in
-the middle of a pattern-filled buffer and require every element outside [0, M) x [0, N) to keep its bits."""
+the middle of a pattern-filled buffer and require every element outside [0, M) x [0, N) to keep its bits; their
+four row strides all differ (lda = K + 8, ldw = K + 16, ldc = N + 8, ldr = N + 16, every operand a view of a wider
+allocation), so a launcher that swaps two of them misses the bound."""
 import math
 
 import pytest
@@ -105,13 +107,15 @@ def _gemm_cases():
     return cases
 
 
-def _operands(cuda, M, N, K, epi, lda=None, ldr=None, seed=0):
-    """Activations randn + 0.5 (a dropped K slab is coherent, not noise), weights randn / sqrt(K), bias and
-    residual randn; a / r optionally as row-strided views."""
+def _operands(cuda, M, N, K, epi, lda=None, ldw=None, ldr=None, seed=0, w8=False):
+    """Activations randn + 0.5 (a dropped K slab is coherent, not noise), weights randn / sqrt(K) (w8: as fp8
+    e4m3fn), bias and residual randn; a / w / r optionally as row-strided views of a wider buffer (the fp8 weights
+    are converted whole and sliced after: .to() on a view packs it)."""
     torch.manual_seed(seed)
-    lda, ldr = lda or K, ldr or N
+    lda, ldw, ldr = lda or K, ldw or K, ldr or N
     a = (torch.randn(M, lda, device=cuda) + 0.5).to(BF)[:, :K]
-    w = (torch.randn(N, K, device=cuda) / math.sqrt(K)).to(BF)
+    w = (torch.randn(N, ldw, device=cuda) / math.sqrt(K)).to(BF)
+    w = (w.to(torch.float8_e4m3fn) if w8 else w)[:, :K]
     b = torch.randn(N, device=cuda).to(BF) if epi != "none" else None
     r = torch.randn(M, ldr, device=cuda).to(BF)[:, :N] if epi == "bias_res" else None
     return a, w, b, r
@@ -142,15 +146,14 @@ def _launch_gemm(name, a, w, c, b, r, M, N, K, ldc):
                                epi, 1.0, s["variant"], core._stream())
 
 
-def _weights_for(name, w):
-    return w.to(torch.float8_e4m3fn) if GEMM_KERNELS[name]["entry"] == "w8" else w
+def _is_w8(name):
+    return GEMM_KERNELS[name]["entry"] == "w8"
 
 
 @pytest.mark.parametrize("epi", EPIS)
 @pytest.mark.parametrize("name,M,N,K", _gemm_cases())
 def test_gemm_bound(cuda, name, M, N, K, epi):
-    a, w, b, r = _operands(cuda, M, N, K, epi)
-    w = _weights_for(name, w)
+    a, w, b, r = _operands(cuda, M, N, K, epi, w8=_is_w8(name))
     out = torch.empty(M, N, device=cuda, dtype=BF)
     assert _launch_gemm(name, a, w, out.data_ptr(), b, r, M, N, K, N) == 0
     ref, tol = gemm_bound(a, w.float(), b, r)
@@ -224,7 +227,7 @@ def _splitk(lib, variant, splits, a, w, c, b, r, M, N, K, ldc, ws):
     flags = (1 if b is not None else 0) | (2 if r is not None else 0)
     assert K % (32 * splits) == 0 and N % 8 == 0
     return lib.cgs_gemm_bf16_splitk(a.data_ptr(), w.data_ptr(), c, _ptr(b), _ptr(r), None, None, M, N, K, a.stride(0),
-                                    K, ldc, r.stride(0) if r is not None else 0, flags, 1.0, splits, variant,
+                                    w.stride(0), ldc, r.stride(0) if r is not None else 0, flags, 1.0, splits, variant,
                                     ws.data_ptr(), ws.numel(), core._stream())
 
 
@@ -267,8 +270,7 @@ def test_gemm_writes_only_its_output(cuda, name):
     s = GEMM_KERNELS[name]
     M, N = _partial_shape(s)
     K = s["min_k"]
-    a, w, b, r = _operands(cuda, M, N, K, "bias_res", lda=K + 8, ldr=N + 8)
-    w = _weights_for(name, w)
+    a, w, b, r = _operands(cuda, M, N, K, "bias_res", lda=K + 8, ldw=K + 16, ldr=N + 16, w8=_is_w8(name))
     buf, before, ldc = _guarded_c(cuda, M, N, s["bm"])
     assert _launch_gemm(name, a, w, buf.data_ptr() + 2 * 4096, b, r, M, N, K, ldc) == 0
     torch.cuda.synchronize()
@@ -291,16 +293,16 @@ def test_gemm_workspace_paths_write_only_their_output(cuda, kind):
         M, N, K = bm - 3, bn - 8, 64
         ws_bytes = lib.cgs_splitk_ws_bytes(M, N, 2)
     assert ws_bytes > 0
-    a, w, b, r = _operands(cuda, M, N, K, "bias_res", lda=K + 8, ldr=N + 8)
+    a, w, b, r = _operands(cuda, M, N, K, "bias_res", lda=K + 8, ldw=K + 16, ldr=N + 16)
     ws = torch.full((int(ws_bytes),), 0x7F, dtype=torch.uint8, device=cuda)
     buf, before, ldc = _guarded_c(cuda, M, N, bm)
     c = buf.data_ptr() + 2 * 4096
     if kind == "v7ws":
-        rc = lib.cgs_gemm_bf16_v7ws(a.data_ptr(), w.data_ptr(), c, b.data_ptr(), r.data_ptr(), M, N, K, K + 8, K, ldc,
-                                    N + 8, 3, 1.0, ws.data_ptr(), ws_bytes, core._stream())
+        rc = lib.cgs_gemm_bf16_v7ws(a.data_ptr(), w.data_ptr(), c, b.data_ptr(), r.data_ptr(), M, N, K, a.stride(0),
+                                    w.stride(0), ldc, r.stride(0), 3, 1.0, ws.data_ptr(), ws_bytes, core._stream())
     elif kind == "skinny_ws":
-        rc = lib.cgs_gemm_skinny_ws(a.data_ptr(), w.data_ptr(), c, b.data_ptr(), r.data_ptr(), M, N, K, K + 8, K, ldc,
-                                    N + 8, 3, 1.0, ws.data_ptr(), ws_bytes, core._stream())
+        rc = lib.cgs_gemm_skinny_ws(a.data_ptr(), w.data_ptr(), c, b.data_ptr(), r.data_ptr(), M, N, K, a.stride(0),
+                                    w.stride(0), ldc, r.stride(0), 3, 1.0, ws.data_ptr(), ws_bytes, core._stream())
     else:
         rc = _splitk(lib, int(kind[6:]), 2, a, w, c, b, r, M, N, K, ldc, ws)
     assert rc == 0
