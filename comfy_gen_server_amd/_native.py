@@ -148,6 +148,9 @@ KERNEL_SIGNATURES = {
     "cgs_gemm_bf16_w8": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _I, _F, _P],
     "cgs_gemm_bf16_v": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _I, _F, _I, _P],
     "cgs_conv2d_nhwc_v": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    # nearest-2x upsample + 3x3 conv from low-resolution tap planes (csrc/kernels/upconv.hip): x, tap-ordered
+    # weights, bias, out, N, H, W, Cin, Cout
+    "cgs_upconv_taps_nhwc": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     # ... + CgsAct code, parameter: act(conv + bias) (+ res) on the mc::tile kernels (variant 3 / 4 / 8)
     "cgs_conv2d_nhwc_act": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F,
                             _P],
@@ -222,11 +225,12 @@ KERNEL_SIGNATURES = {
     "cgs_ln_rs_from_partials": [_P, _P, _I, _I, _F, _P],
     # v6 conv gather override (-1 auto, 1 ConvGatherK, 0 ConvGatherA8): in-process A/B
     "cgs_conv_v6_set_loader": [_I],
+    "cgs_upconv_set_tile_group": [_I],
 }
 
 
 _RESTYPE = {"cgs_groupnorm_workspace": ctypes.c_longlong, "cgs_splitk_ws_bytes": ctypes.c_longlong, "cgs_groupnorm_f32_ws": ctypes.c_longlong, "cgs_grn_slices": ctypes.c_int, "cgs_v7_ws_bytes": ctypes.c_longlong, "cgs_gemm_skinny_ws_bytes": ctypes.c_longlong, "cgs_gemm_set_variant": None, "cgs_v7_set_dbg": None, "cgs_v6_set_mode": None, "cgs_attn_set_prio": None, "cgs_gn_set_blocks": None, "cgs_conv_smalln_set_lds": None, "cgs_attn_set_kv2_rows": None, "cgs_grn_set_rows": None,
-            "cgs_conv_set_variant": None, "cgs_set_tile_group": None, "cgs_conv_set_tile_group": None, "cgs_dwconv_set_px": None,
+            "cgs_conv_set_variant": None, "cgs_set_tile_group": None, "cgs_conv_set_tile_group": None, "cgs_dwconv_set_px": None, "cgs_upconv_set_tile_group": None,
             "cgs_attn_set_variant": None,
             "cgs_conv_v6_set_loader": None}
 

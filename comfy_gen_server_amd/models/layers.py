@@ -148,6 +148,10 @@ class Conv2d(nn.Module, DerivedMixin, CastWeightBiasOp):
     def weight_nhwc(self):
         return self._derived_get("w_nhwc", lambda: self.weight.permute(0, 2, 3, 1).contiguous())
 
+    def weight_taps(self):
+        """The tap-ordered copy for the tap form of the upsample conv (``ops.core.upconv_tap_weights``)."""
+        return self._derived_get("w_taps", lambda: ops.core.upconv_tap_weights(self.weight))
+
     def forward(self, x, residual=None, upsample2x=False, x2=None, gn_stats=False, act=None, act_param=0.0):
         """``x2``: convolve cat([x, x2], 1) without materialising the concat (K14). ``gn_stats``: the next op
         is a GroupNorm over the output (``ops.conv2d`` statistics partials from the epilogue). ``act`` /
@@ -186,8 +190,12 @@ class Conv2d(nn.Module, DerivedMixin, CastWeightBiasOp):
             x = xp
         elif x.is_cuda and self.groups == 1:
             wn = self.weight_nhwc()
+        wt = None
+        if upsample2x and wn is not None and w is self.weight and tuple(self.kernel_size) == (3, 3):
+            wt = self.weight_taps     # built on first use, and only where the op takes the tap form
         return ops.conv2d(x, w, b, self.stride, self.padding, residual=residual, weight_nhwc=wn,
-                          groups=self.groups, upsample2x=upsample2x, gn_stats=gn_stats, act=act, act_param=act_param)
+                          groups=self.groups, upsample2x=upsample2x, gn_stats=gn_stats, act=act, act_param=act_param,
+                          weight_taps=wt)
 
 
 class Conv3d(nn.Module, DerivedMixin):

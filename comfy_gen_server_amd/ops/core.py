@@ -878,19 +878,22 @@ def _spatial():
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, stride=1, padding=0,
            residual: torch.Tensor | None = None, weight_nhwc: torch.Tensor | None = None,
            groups: int = 1, upsample2x: bool = False, x2: torch.Tensor | None = None,
-           gn_stats: bool = False, act: str | None = None, act_param: float = 0.0) -> torch.Tensor:
+           gn_stats: bool = False, act: str | None = None, act_param: float = 0.0,
+           weight_taps=None) -> torch.Tensor:
     """2-D convolution; inside a row-sharded UNet call (latency mode, parallel/spatial.py) the halo rows
     come from the neighbouring ranks and the residual is added to the kept interior. ``gn_stats``: when the
     shape runs on the v6 kernel, its epilogue also writes GroupNorm statistics partials of the output
     (per image, 64-pixel block and channel), attached as ``y._cgs_gnpart`` -- ``group_norm`` over y then
     skips its statistics pass. ``act`` (a name of ``ACT_CODES``; ``act_param``: the leaky_relu slope):
-    y = act(conv(x) + bias) (+ residual), see ``_conv2d_act``."""
+    y = act(conv(x) + bias) (+ residual), see ``_conv2d_act``. ``weight_taps``: the layer's cached
+    ``upconv_tap_weights`` copy (a tensor, or a callable that returns it) for the tap form of ``upsample2x``."""
     if act is not None:
         return _conv2d_act(x, weight, bias, stride, padding, residual, weight_nhwc, groups, upsample2x, x2, act,
                            float(act_param))
     sc = _spatial()
     if sc is None:
-        return _conv2d(x, weight, bias, stride, padding, residual, weight_nhwc, groups, upsample2x, x2, gn_stats)
+        return _conv2d(x, weight, bias, stride, padding, residual, weight_nhwc, groups, upsample2x, x2, gn_stats,
+                       weight_taps)
     st = stride[0] if isinstance(stride, (tuple, list)) else stride
     pd = padding[0] if isinstance(padding, (tuple, list)) else padding
     y = sc.conv2d(lambda xx, _: _conv2d(xx, weight, bias, st, pd, None, weight_nhwc, groups, upsample2x, None),
@@ -898,6 +901,29 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, str
     if residual is not None:
         y = y + residual
     return y.contiguous(memory_format=torch.channels_last) if y.is_cuda else y
+
+
+def upconv_tap_weights(weight: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> the tap-ordered copy of the upsample conv's tap form, [ceil(Cout / 16) * 144, Cin]:
+    row (g * 9 + 3 dy + dx) * 16 + c is W[16 g + c, :, dy, dx]; the rows of channels past Cout are zeros. A
+    derived copy like ``weight_nhwc``: layers cache it (``Conv2d.weight_taps``)."""
+    Cout, Cin = weight.shape[:2]
+    G = (Cout + 15) // 16
+    w = weight.new_zeros((G * 16, Cin, 9))
+    w[:Cout] = weight.reshape(Cout, Cin, 9)
+    return w.view(G, 16, Cin, 9).permute(0, 3, 1, 2).contiguous().view(G * 144, Cin)
+
+
+def _upconv_use_taps(N, H, W, Cin, Cout, cached) -> bool:
+    """The tap form or CONV_UP2X for a legal upsample conv. ``CGS_UPCONV_TAPS=1`` forces the tap form, ``0`` the
+    old kernel (A/B runs; read per call). Otherwise a size rule from the measured shapes (profiles/r07): the tap
+    form won 1.5-2.1x on every SDXL UNet / VAE upsample conv, batch 1 to 16, Cin = 256 ... 1280, and its gain falls
+    with Cin as the combine grows against the GEMM -- so Cin >= 256, Cout >= 32, the problem sizes the conv
+    variants are tuned from, and a caller that holds the tap-ordered weight copy; everything else stays."""
+    mode = os.environ.get("CGS_UPCONV_TAPS", "")
+    if mode in ("0", "1"):
+        return mode == "1"
+    return cached and Cin >= 256 and Cout >= 32 and N * H * W * Cin * Cout * 36 >= (1 << 27)
 
 
 _FUSED_ACT_CONV = {"v3": 3, "v4": 4, "v8": 8}     # the mc::tile convs: their epilogue carries the activation
@@ -962,13 +988,15 @@ def _conv2d_act(x, weight, bias, stride, padding, residual, weight_nhwc, groups,
 def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, stride=1, padding=0,
             residual: torch.Tensor | None = None, weight_nhwc: torch.Tensor | None = None,
             groups: int = 1, upsample2x: bool = False, x2: torch.Tensor | None = None,
-            gn_stats: bool = False) -> torch.Tensor:
+            gn_stats: bool = False, weight_taps=None) -> torch.Tensor:
     """2-D convolution (K09/K10/K12). Device path: implicit-GEMM NHWC kernel on MFMA
     (csrc/kernels/conv.hip) with fused bias + residual epilogue; ``weight_nhwc`` = weight permuted
     to [Cout, kh, kw, Cin]. ``upsample2x`` reads the input through a nearest-2x upsample inside the
     kernel (openaimodel.py Upsample: interpolate + conv) so the 4x tensor is never written.
     ``x2``: convolve ``cat([x, x2], 1)`` with the concat never materialised (K14; the kernel's A-loader
-    picks the source per 64-channel K step, so both channel counts must be multiples of 64)."""
+    picks the source per 64-channel K step, so both channel counts must be multiples of 64).
+    The plain 3 x 3 / stride 1 / pad 1 ``upsample2x`` conv (one source, no residual) also has the tap form
+    (csrc/kernels/upconv.hip: each tap product once at low resolution); see ``_upconv_use_taps``."""
     if isinstance(stride, (tuple, list)):
         stride = stride[0]
     if isinstance(padding, (tuple, list)):
@@ -986,6 +1014,7 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
               and x.dim() == 4 and cin_total % 32 == 0 and (Cout % 8 == 0 or Cout <= 16 or cin_total % 64 == 0))
     dual_ok = x2 is None or (hip_ok and x.shape[1] % 64 == 0 and x2.shape[1] % 64 == 0 and x2.dtype == x.dtype
                              and not upsample2x and Cout % 8 == 0)
+    single = x2 is None       # the tap form of the upsample conv is for one source as the caller gave it
     if x2 is not None and not dual_ok:
         # every path other than the dual-source HIP loader convolves the materialised concat
         x = torch.cat([x, x2.to(x.dtype)], dim=1)
@@ -1037,6 +1066,21 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
                                      + ((("dual", C1),) if x2c is not None else ()), cands, default="auto")
             variant = {"v2": 2, "v4": 4, "v5": 5, "v6": 6, "v7": 7, "v8": 8, "v6n128": 18, "v6w4": 21,
                        "auto": -2}[choice]
+        if (upsample2x and single and r is None and not gn_stats and kh == 3 and kw == 3 and stride == 1
+                and padding == 1 and Cout % 8 == 0 and weight.dtype == x.dtype
+                and _native.has_kernel("cgs_upconv_taps_nhwc")):
+            def run_taps():
+                wt = weight_taps() if callable(weight_taps) else weight_taps
+                if wt is None:
+                    wt = upconv_tap_weights(weight)
+                out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=x.dtype,
+                                  memory_format=torch.channels_last)
+                _check(_lib().cgs_upconv_taps_nhwc(xc.data_ptr(), wt.data_ptr(), _ptr(bias), out.data_ptr(), N, H, W,
+                                                   Cin, Cout, _stream()), "cgs_upconv_taps_nhwc")
+                return out
+
+            if _upconv_use_taps(N, H, W, Cin, Cout, weight_taps is not None):
+                return run_taps()
         if (gn_stats and variant == 6 and _GNS and (Ho * Wo) % 256 == 0 and Cin % 64 == 0 and C1 % 64 == 0
                 and Cout % 8 == 0 and kh * kw * Cin >= 128 and (bias is None or bias.data_ptr() % 8 == 0)
                 and _native.has_kernel("cgs_conv2d_nhwc_gns")):
