@@ -959,126 +959,140 @@ CGS_EXPORT int cgs_transpose_bf16(const void* x, void* y, int rows, int cols, lo
   return (int)hipGetLastError();
 }
 
-static int g_attn_variant = 0;   // 0 auto, 1 generic kernel, 2 D=64 fast kernel (256-row Q blocks), 3 short-KV
-                                 // kernel, 4 D=64 r2, 5 D=64 fast kernel with 128-row Q blocks
+// Process-wide kernel choice of cgs_flash_attn_fwd / _lse (cgs_flash_attn_fwd_v takes its own per call): 0 auto,
+// 1 generic kernel, 2 D=64 fast kernel (256-row Q blocks), 3 short-KV kernel, 4 the path of 2 (once a second D=64
+// kernel; unlike 2 it falls through to the generic kernel outside the fast one's domain), 5 D=64 fast kernel with
+// 128-row Q blocks
+static int g_attn_variant = 0;
 CGS_EXPORT void cgs_attn_set_variant(int v) { g_attn_variant = v; }
 // s_setprio(1) around the P.V MFMAs of the D = 64 kernel (default on: +1.5 / +2.2 % at SDXL levels 1 / 2,
 // profiles/r03/attn_setprio_pv.log); cgs_attn_set_prio(0) selects the 8-wave form without it (A/B)
 static bool g_attn_prio = true;
 CGS_EXPORT void cgs_attn_set_prio(int on) { g_attn_prio = on != 0; }
 
-static int flash_attn_impl(const void* q, const void* k, const void* v, void* o, int B, int H, int Sq, int Sk, int D,
-                           long long qsb, long long qss, long long qsh, long long ksb, long long kss, long long ksh,
-                           long long vsb, long long vss, long long vsh, long long osb, long long oss, long long osh,
-                           float scale, const void* key_mask, int causal, float* lse, hipStream_t stream) {
-  if (D % 8) return (int)hipErrorInvalidValue;
-  int nqb = (Sq + ATT_QB - 1) / ATT_QB;
-  long long nwg = (long long)nqb * B * H;
-  if (nwg > 0x7fffffff) return (int)hipErrorInvalidValue;
-  float sl2 = scale * 1.4426950408889634f;
-  const bool al16 = ((qss | kss | vss | oss | qsb | ksb | vsb | osb | qsh | ksh | vsh | osh) & 7) == 0 &&
-                    ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
-                      reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o)) & 15) == 0;
-  if (D == 64 && !key_mask && !causal && al16 && Sk > 0 && Sk <= 128 && !lse &&
-      (g_attn_variant == 0 || g_attn_variant == 3)) {
+// The operands of one attention call: built once per exported entry from its parameter list and passed by reference
+// below that (as GemmArgs is for the GEMMs). Strides in elements per batch entry (sb), token (ss) and head (sh).
+struct AttnArgs {
+  const void *q, *k, *v;   // bf16
+  void* o;
+  int B, H, Sq, Sk, D;
+  long long qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh;
+  float scale;
+  const void* key_mask;    // int8 [B, Sk] or null (generic kernel only)
+  int causal;
+  float* lse;              // fp32 [B, H, Sq] out, or null
+  hipStream_t stream;
+
+  bool al16() const {      // 16-B aligned operands and rows (the D = 64, short-KV and wide kernels)
+    return ((qss | kss | vss | oss | qsb | ksb | vsb | osb | qsh | ksh | vsh | osh) & 7) == 0 &&
+           ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+             reinterpret_cast<uintptr_t>(o)) & 15) == 0;
+  }
+  float sl2() const { return scale * 1.4426950408889634f; }   // exp2 in the kernels: log2(e) folded into the scale
+  // *nqb Q blocks of ``rows`` queries, *g the 1-D grid of nqb * B * H * splits workgroups; false if that overflows
+  bool grid(int rows, int* nqb, dim3* g, int splits = 1) const {
+    *nqb = (Sq + rows - 1) / rows;
+    const long long nwg = (long long)*nqb * B * H * splits;
+    *g = dim3((unsigned)nwg);
+    return nwg <= 0x7fffffff;
+  }
+};
+
+// Launch a kernel whose parameters begin (q, k, v, o, H, Sq, Sk, the twelve strides, c, nqb): the D = 64, short-KV
+// and wide kernels. tail follows the prefix; it names every later parameter (no defaults through a pointer).
+template <typename Kern, typename... Tail>
+static void launch_attn(Kern kern, dim3 grid, int block, const AttnArgs& a, int nqb, Tail... tail) {
+  kern<<<grid, block, 0, a.stream>>>((const u16*)a.q, (const u16*)a.k, (const u16*)a.v, (u16*)a.o, a.H, a.Sq, a.Sk,
+                                     a.qsb, a.qss, a.qsh, a.ksb, a.kss, a.ksh, a.vsb, a.vss, a.vsh, a.osb, a.oss,
+                                     a.osh, a.sl2(), nqb, tail...);
+}
+
+// The generic kernel for the next head dim >= D it is built for (null: D > 160), and its launch
+using FlashKernel = decltype(&flash_fwd_kernel<32>);
+template <bool BIAS>
+static FlashKernel flash_kernel(int D) {
+  if (D <= 32) return flash_fwd_kernel<32, BIAS>;
+  if (D <= 64) return flash_fwd_kernel<64, BIAS>;
+  if (D <= 96) return flash_fwd_kernel<96, BIAS>;
+  if (D <= 128) return flash_fwd_kernel<128, BIAS>;
+  if (D <= 160) return flash_fwd_kernel<160, BIAS>;
+  return nullptr;
+}
+static void launch_flash(FlashKernel kern, dim3 grid, const AttnArgs& a, int nqb, AttnBias ab) {
+  kern<<<grid, 256, 0, a.stream>>>((const u16*)a.q, (const u16*)a.k, (const u16*)a.v, (u16*)a.o, a.B, a.H, a.Sq, a.Sk,
+                                   a.D, a.qsb, a.qss, a.qsh, a.ksb, a.kss, a.ksh, a.vsb, a.vss, a.vsh, a.osb, a.oss,
+                                   a.osh, a.sl2(), (const signed char*)a.key_mask, a.causal, nqb, a.lse, ab);
+}
+
+// The short-KV kernel for Sk keys (32-key tiles) and qi 128-query blocks per workgroup, with or without s_setprio
+using SkvKernel = decltype(&attn_fwd_d64_shortkv_kernel<1>);
+template <int NKT, bool PRIO>
+static SkvKernel skv_qi(int qi) {
+  if (qi == 4) return attn_fwd_d64_shortkv_kernel<NKT, PRIO, 4>;
+  return qi == 2 ? attn_fwd_d64_shortkv_kernel<NKT, PRIO, 2> : attn_fwd_d64_shortkv_kernel<NKT, PRIO, 1>;
+}
+template <bool PRIO>
+static SkvKernel skv_kernel(int Sk, int qi) {
+  return Sk <= 32 ? skv_qi<1, PRIO>(qi) : Sk <= 64 ? skv_qi<2, PRIO>(qi) : Sk <= 96 ? skv_qi<3, PRIO>(qi) : skv_qi<4, PRIO>(qi);
+}
+
+// Q rows per workgroup of the D = 64 kernel: 256 (8 waves) unless the 128-row form (4 waves, two workgroups per CU)
+// is asked for, or is picked automatically because ``fill`` x the 256-row grid is under one round of the CUs
+static int d64_rows(const AttnArgs& a, bool ask128, bool automatic, int fill) {
+  const long long nwg256 = (long long)((a.Sq + 255) / 256) * a.B * a.H;
+  return ask128 || (automatic && nwg256 * fill < num_cus()) ? 128 : 256;
+}
+static const KV2 kNoKV2{nullptr, nullptr, 0, 0, 0, 0, 0};
+
+// variant: as cgs_attn_set_variant
+static int flash_attn_dispatch(const AttnArgs& a, int variant) {
+  int nqb;
+  dim3 grid;
+  if (a.D % 8 || !a.grid(ATT_QB, &nqb, &grid)) return (int)hipErrorInvalidValue;
+  const bool tiled = !a.key_mask && !a.causal && a.al16() && a.Sk > 0;   // every kernel but the generic one needs it
+  if (a.D == 64 && tiled && a.Sk <= 128 && !a.lse && (variant == 0 || variant == 3)) {
     // QI 32-query blocks per wave (K / V staged once per 128 * QI queries): measured +4.5 % at SDXL level 1
     // (Sq = 4096), -2.6 % at level 2 (profiles/r04/shortkv_qi_ab_r04al.log) -> QI = 4 for Sq >= 2048 while
     // that leaves >= 2 workgroups per CU; CGS_SKV_QI=1|2|4 overrides (A/B)
-    const long long blocks128 = (long long)((Sq + 127) / 128) * B * H;
+    const long long blocks128 = (long long)((a.Sq + 127) / 128) * a.B * a.H;
     static const int qi_env = getenv("CGS_SKV_QI") ? atoi(getenv("CGS_SKV_QI")) : 0;
     int qi = 1;
     if (qi_env == 1 || qi_env == 2 || qi_env == 4) qi = qi_env;
-    else if (Sq >= 2048 && blocks128 / 4 >= 2 * num_cus()) qi = 4;
-    const int nqb3 = (Sq + 128 * qi - 1) / (128 * qi);
-    const long long nwg3 = (long long)nqb3 * B * H;
-    if (nwg3 > 0x7fffffff) return (int)hipErrorInvalidValue;
-#define SKV_GO(NKT, QIV)                                                                                             \
-  do {                                                                                                              \
-    if (g_attn_prio)                                                                                                \
-      attn_fwd_d64_shortkv_kernel<NKT, true, QIV><<<dim3((unsigned)nwg3), 256, 0, stream>>>(                        \
-          (const u16*)q, (const u16*)k, (const u16*)v, (u16*)o, H, Sq, Sk, qsb, qss, qsh, ksb, kss, ksh, vsb, vss,   \
-          vsh, osb, oss, osh, sl2, nqb3);                                                                           \
-    else                                                                                                            \
-      attn_fwd_d64_shortkv_kernel<NKT, false, QIV><<<dim3((unsigned)nwg3), 256, 0, stream>>>(                       \
-          (const u16*)q, (const u16*)k, (const u16*)v, (u16*)o, H, Sq, Sk, qsb, qss, qsh, ksb, kss, ksh, vsb, vss,   \
-          vsh, osb, oss, osh, sl2, nqb3);                                                                           \
-  } while (0)
-#define SKV_LAUNCH(NKT)                                                                                              \
-  do {                                                                                                              \
-    if (qi == 4) SKV_GO(NKT, 4);                                                                                    \
-    else if (qi == 2) SKV_GO(NKT, 2);                                                                               \
-    else SKV_GO(NKT, 1);                                                                                            \
-  } while (0)
-    if (Sk <= 32) SKV_LAUNCH(1);
-    else if (Sk <= 64) SKV_LAUNCH(2);
-    else if (Sk <= 96) SKV_LAUNCH(3);
-    else SKV_LAUNCH(4);
-#undef SKV_GO
-#undef SKV_LAUNCH
+    else if (a.Sq >= 2048 && blocks128 / 4 >= 2 * num_cus()) qi = 4;
+    if (!a.grid(128 * qi, &nqb, &grid)) return (int)hipErrorInvalidValue;
+    launch_attn(g_attn_prio ? skv_kernel<true>(a.Sk, qi) : skv_kernel<false>(a.Sk, qi), grid, 256, a, nqb);
     return (int)hipGetLastError();
   }
-  if (g_attn_variant == 3) return (int)hipErrorInvalidValue;
-  if (D == WD_D) {
-    if (key_mask || causal || !al16 || Sk <= 0 || lse) return (int)hipErrorInvalidValue;
-    const int nqb4 = (Sq + 31) / 32;
-    const long long nwg4 = (long long)nqb4 * B * H;
-    if (nwg4 > 0x7fffffff) return (int)hipErrorInvalidValue;
-    attn_fwd_wide_kernel<<<dim3((unsigned)nwg4), 256, 0, stream>>>(
-        (const u16*)q, (const u16*)k, (const u16*)v, (u16*)o, H, Sq, Sk, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh,
-        osb, oss, osh, sl2, nqb4);
+  if (variant == 3) return (int)hipErrorInvalidValue;
+  if (a.D == WD_D) {
+    if (!tiled || a.lse || !a.grid(32, &nqb, &grid)) return (int)hipErrorInvalidValue;
+    launch_attn(attn_fwd_wide_kernel, grid, 256, a, nqb);
     return (int)hipGetLastError();
   }
-  if (D == 64 && !key_mask && !causal && al16 && g_attn_variant != 1 && Sk > 0) {
-    // 256-row Q blocks (8 waves) unless that leaves the grid under one round of the CUs and the
-    // 128-row form (4 waves, two WGs per CU) is asked for (variant 5) or auto-picked (variant 0)
-    const long long nwg256 = (long long)((Sq + 255) / 256) * B * H;
-    const bool small = g_attn_variant == 5 || (g_attn_variant == 0 && nwg256 < num_cus());
-    const int rows = small ? 128 : 256;
-    int nqb2 = (Sq + rows - 1) / rows;
-    long long nwg2 = (long long)nqb2 * B * H;
-    if (nwg2 > 0x7fffffff) return (int)hipErrorInvalidValue;
-    if (small)
-      attn_fwd_d64_kernel<4><<<dim3((unsigned)nwg2), 256, 0, stream>>>(
-          (const u16*)q, (const u16*)k, (const u16*)v, (u16*)o, H, Sq, Sk, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh,
-          osb, oss, osh, sl2, nqb2, lse);
-    else if (!g_attn_prio)
-      attn_fwd_d64_kernel<8, false, false><<<dim3((unsigned)nwg2), 512, 0, stream>>>(
-          (const u16*)q, (const u16*)k, (const u16*)v, (u16*)o, H, Sq, Sk, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh,
-          osb, oss, osh, sl2, nqb2, lse);
-    else
-      attn_fwd_d64_kernel<8><<<dim3((unsigned)nwg2), 512, 0, stream>>>(
-          (const u16*)q, (const u16*)k, (const u16*)v, (u16*)o, H, Sq, Sk, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh,
-          osb, oss, osh, sl2, nqb2, lse);
+  if (a.D == 64 && tiled && variant != 1) {
+    const int rows = d64_rows(a, variant == 5, variant == 0, 1);
+    if (!a.grid(rows, &nqb, &grid)) return (int)hipErrorInvalidValue;
+    if (rows == 128) launch_attn(attn_fwd_d64_kernel<4>, grid, 256, a, nqb, a.lse, kNoKV2, 0LL);
+    else if (!g_attn_prio) launch_attn(attn_fwd_d64_kernel<8, false, false>, grid, 512, a, nqb, a.lse, kNoKV2, 0LL);
+    else launch_attn(attn_fwd_d64_kernel<8>, grid, 512, a, nqb, a.lse, kNoKV2, 0LL);
     return (int)hipGetLastError();
   }
-  if (g_attn_variant == 2) return (int)hipErrorInvalidValue;
-  dim3 grid((unsigned)nwg);
-#define ATT_LAUNCH(DPV)                                                                                         \
-  flash_fwd_kernel<DPV><<<grid, 256, 0, stream>>>((const u16*)q, (const u16*)k, (const u16*)v, (u16*)o, B, H, Sq, \
-                                                   Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss,  \
-                                                   osh, sl2, (const signed char*)key_mask, causal, nqb, lse)
-  if (D <= 32) ATT_LAUNCH(32);
-  else if (D <= 64) ATT_LAUNCH(64);
-  else if (D <= 96) ATT_LAUNCH(96);
-  else if (D <= 128) ATT_LAUNCH(128);
-  else if (D <= 160) ATT_LAUNCH(160);
-  else return (int)hipErrorInvalidValue;
-#undef ATT_LAUNCH
+  if (variant == 2) return (int)hipErrorInvalidValue;
+  const FlashKernel kern = flash_kernel<false>(a.D);
+  if (!kern) return (int)hipErrorInvalidValue;
+  launch_flash(kern, grid, a, nqb, AttnBias{nullptr, nullptr, nullptr, 1});
   return (int)hipGetLastError();
 }
 
-// Per-call kernel choice for the op-layer autotuner (variant as in cgs_attn_set_variant; the process
-// setting is restored before returning).
+// Per-call kernel choice for the op-layer autotuner (variant as in cgs_attn_set_variant, which this call neither
+// reads nor changes: concurrent callers each get the kernel they asked for).
 CGS_EXPORT int cgs_flash_attn_fwd_v(const void* q, const void* k, const void* v, void* o, int B, int H, int Sq, int Sk,
                                     int D, long long qsb, long long qss, long long qsh, long long ksb, long long kss,
                                     long long ksh, long long vsb, long long vss, long long vsh, long long osb,
                                     long long oss, long long osh, float scale, int variant, hipStream_t stream) {
-  const int saved = g_attn_variant;
-  g_attn_variant = variant;
-  const int rc = flash_attn_impl(q, k, v, o, B, H, Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh,
-                                 scale, nullptr, 0, nullptr, stream);
-  g_attn_variant = saved;
-  return rc;
+  const AttnArgs a{q, k, v, o, B, H, Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, scale,
+                   nullptr, 0, nullptr, stream};
+  return flash_attn_dispatch(a, variant);
 }
 
 // Merge of the KS key-split partials: O = sum_s exp(lse_s - L) O_s with L = log sum_s exp(lse_s) (every
@@ -1129,33 +1143,25 @@ CGS_EXPORT int cgs_flash_attn_fwd_ks(const void* q, const void* k, const void* v
                                      long long vss, long long osb, long long oss, float scale, int KS, void* ws_o,
                                      void* ws_lse, hipStream_t stream) {
   if ((KS != 2 && KS != 4) || B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || !ws_o || !ws_lse) return (int)hipErrorInvalidValue;
-  const bool al16 = ((qss | qsb | kss | ksb | vss | vsb | oss | osb) & 7) == 0 &&
-                    ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-                      reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(ws_o)) & 15) == 0;
+  const AttnArgs a{q, k, v, o, B, H, Sq, Sk, 64, qsb, qss, 64, ksb, kss, 64, vsb, vss, 64, osb, oss, 64, scale,
+                   nullptr, 0, nullptr, stream};
+  const bool al16 = a.al16() && (reinterpret_cast<uintptr_t>(ws_o) & 15) == 0;
   const int tiles = (Sk + 63) / 64;
   const int tps = (tiles + KS - 1) / KS;
   if (!al16 || (long long)(KS - 1) * tps * 64 >= Sk) return (int)hipErrorInvalidValue;   // every split has keys
-  const int nqb = (Sq + 255) / 256;
-  const long long nwg = (long long)nqb * B * H * KS;
+  int nqb;
+  dim3 grid;
   const long long ospl = (long long)B * Sq * H * 64;
-  if (nwg > 0x7fffffff || ospl * KS > 0x7fffffffffffll) return (int)hipErrorInvalidValue;
-  const float sl2 = scale * 1.4426950408889634f;
-  const long long wsb = (long long)Sq * H * 64, wss = (long long)H * 64;
-#define CGS_KS_GO(KV)                                                                                              \
-  attn_fwd_d64_kernel<8, false, true, KV><<<dim3((unsigned)nwg), 512, 0, stream>>>(                                \
-      (const u16*)q, (const u16*)k, (const u16*)v, (u16*)ws_o, H, Sq, Sk, qsb, qss, 64, ksb, kss, 64, vsb, vss, 64,   \
-      wsb, wss, 64, sl2, nqb, (float*)ws_lse, KV2{nullptr, nullptr, 0, 0, 0, 0, 0}, ospl)
-  if (KS == 2) CGS_KS_GO(2); else CGS_KS_GO(4);
-#undef CGS_KS_GO
+  if (!a.grid(256, &nqb, &grid, KS) || ospl * KS > 0x7fffffffffffll) return (int)hipErrorInvalidValue;
+  AttnArgs w = a;   // the splits write token-major partials and their log-sum-exp to the workspaces
+  w.o = ws_o, w.osb = (long long)Sq * H * 64, w.oss = (long long)H * 64, w.lse = (float*)ws_lse;
+  if (KS == 2) launch_attn(attn_fwd_d64_kernel<8, false, true, 2>, grid, 512, w, nqb, w.lse, kNoKV2, ospl);
+  else launch_attn(attn_fwd_d64_kernel<8, false, true, 4>, grid, 512, w, nqb, w.lse, kNoKV2, ospl);
   const long long thr = (long long)B * Sq * H * 8;
   long long nb = (thr + 255) / 256;
   const int blocks = (int)(nb > 16384 ? 16384 : nb);
-  if (KS == 2)
-    attn_ks_combine_kernel<2><<<blocks, 256, 0, stream>>>((const u16*)ws_o, (const float*)ws_lse, (u16*)o, B, H, Sq,
-                                                          ospl, osb, oss, 64);
-  else
-    attn_ks_combine_kernel<4><<<blocks, 256, 0, stream>>>((const u16*)ws_o, (const float*)ws_lse, (u16*)o, B, H, Sq,
-                                                          ospl, osb, oss, 64);
+  const auto combine = KS == 2 ? attn_ks_combine_kernel<2> : attn_ks_combine_kernel<4>;
+  combine<<<blocks, 256, 0, stream>>>((const u16*)ws_o, (const float*)ws_lse, (u16*)o, B, H, Sq, ospl, osb, oss, 64);
   return (int)hipGetLastError();
 }
 
@@ -1170,30 +1176,21 @@ CGS_EXPORT int cgs_flash_attn_fwd_kv2(const void* q, const void* k1, const void*
                                       long long k2ss, long long v2sb, long long v2ss, long long osb, long long oss,
                                       float scale, hipStream_t stream) {
   const int Sk = Sk1 + Sk2;
-  const bool al16 = ((qss | qsb | k1sb | k1ss | v1sb | v1ss | k2sb | k2ss | v2sb | v2ss | osb | oss) & 7) == 0 &&
-                    ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k1) | reinterpret_cast<uintptr_t>(v1) |
-                      reinterpret_cast<uintptr_t>(k2) | reinterpret_cast<uintptr_t>(v2) | reinterpret_cast<uintptr_t>(o)) &
-                     15) == 0;
+  const AttnArgs a{q, k1, v1, o, B, H, Sq, Sk, 64, qsb, qss, 64, k1sb, k1ss, 64, v1sb, v1ss, 64, osb, oss, 64, scale,
+                   nullptr, 0, nullptr, stream};
+  const bool al16 = a.al16() && ((k2sb | k2ss | v2sb | v2ss) & 7) == 0 &&
+                    ((reinterpret_cast<uintptr_t>(k2) | reinterpret_cast<uintptr_t>(v2)) & 15) == 0;
   if (!al16 || Sk1 <= 0 || Sk2 <= 0 || Sq <= 0 || B <= 0 || H <= 0) return (int)hipErrorInvalidValue;
-  const long long nwg256 = (long long)((Sq + 255) / 256) * B * H;
-  // 128-row blocks only for tiny grids: at Cascade batch 1 (B x H = 64 / 40, 576 / 1024 queries: 192 / 160
-  // workgroups of 256 rows) the 256-row form measured 13-16 % faster than the 128-row one it used to pick
-  // below one round of CUs (profiles/r05/attn_kv2_rows.md)
-  const bool small = g_kv2_rows == 128 || (g_kv2_rows == 0 && nwg256 * 4 < num_cus());
-  const int rows = small ? 128 : 256;
-  const int nqb2 = (Sq + rows - 1) / rows;
-  const long long nwg2 = (long long)nqb2 * B * H;
-  if (nwg2 > 0x7fffffff) return (int)hipErrorInvalidValue;
-  const float sl2 = scale * 1.4426950408889634f;
+  // 128-row blocks only for tiny grids (under a quarter of a round of CUs): at Cascade batch 1 (B x H = 64 / 40,
+  // 576 / 1024 queries: 192 / 160 workgroups of 256 rows) the 256-row form measured 13-16 % faster than the
+  // 128-row one it used to pick below one round of CUs (profiles/r05/attn_kv2_rows.md)
+  const int rows = d64_rows(a, g_kv2_rows == 128, g_kv2_rows == 0, 4);
+  int nqb;
+  dim3 grid;
+  if (!a.grid(rows, &nqb, &grid)) return (int)hipErrorInvalidValue;
   const KV2 kv2{(const u16*)k2, (const u16*)v2, Sk1, k2sb, k2ss, v2sb, v2ss};
-  if (small)
-    attn_fwd_d64_kernel<4, true><<<dim3((unsigned)nwg2), 256, 0, stream>>>(
-        (const u16*)q, (const u16*)k1, (const u16*)v1, (u16*)o, H, Sq, Sk, qsb, qss, 64, k1sb, k1ss, 64, v1sb, v1ss, 64,
-        osb, oss, 64, sl2, nqb2, nullptr, kv2);
-  else
-    attn_fwd_d64_kernel<8, true><<<dim3((unsigned)nwg2), 512, 0, stream>>>(
-        (const u16*)q, (const u16*)k1, (const u16*)v1, (u16*)o, H, Sq, Sk, qsb, qss, 64, k1sb, k1ss, 64, v1sb, v1ss, 64,
-        osb, oss, 64, sl2, nqb2, nullptr, kv2);
+  if (rows == 128) launch_attn(attn_fwd_d64_kernel<4, true>, grid, 256, a, nqb, a.lse, kv2, 0LL);
+  else launch_attn(attn_fwd_d64_kernel<8, true>, grid, 512, a, nqb, a.lse, kv2, 0LL);
   return (int)hipGetLastError();
 }
 
@@ -1206,22 +1203,12 @@ CGS_EXPORT int cgs_flash_attn_fwd_bias(const void* q, const void* k, const void*
                                        long long osb, long long oss, long long osh, float scale, const float* bias,
                                        const float* mask, int nW, const float* hscale, hipStream_t stream) {
   if (D % 8 || D > 160 || !bias || nW <= 0 || B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return (int)hipErrorInvalidValue;
-  const int nqb = (Sq + ATT_QB - 1) / ATT_QB;
-  const long long nwg = (long long)nqb * B * H;
-  if (nwg > 0x7fffffff) return (int)hipErrorInvalidValue;
-  const float sl2 = scale * 1.4426950408889634f;
-  const AttnBias ab{bias, mask, hscale, nW};
-  dim3 grid((unsigned)nwg);
-#define ATTB_LAUNCH(DPV)                                                                                          \
-  flash_fwd_kernel<DPV, true><<<grid, 256, 0, stream>>>((const u16*)q, (const u16*)k, (const u16*)v, (u16*)o, B, H, \
-                                                        Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, \
-                                                        oss, osh, sl2, nullptr, 0, nqb, nullptr, ab)
-  if (D <= 32) ATTB_LAUNCH(32);
-  else if (D <= 64) ATTB_LAUNCH(64);
-  else if (D <= 96) ATTB_LAUNCH(96);
-  else if (D <= 128) ATTB_LAUNCH(128);
-  else ATTB_LAUNCH(160);
-#undef ATTB_LAUNCH
+  const AttnArgs a{q, k, v, o, B, H, Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, scale,
+                   nullptr, 0, nullptr, stream};
+  int nqb;
+  dim3 grid;
+  if (!a.grid(ATT_QB, &nqb, &grid)) return (int)hipErrorInvalidValue;
+  launch_flash(flash_kernel<true>(D), grid, a, nqb, AttnBias{bias, mask, hscale, nW});
   return (int)hipGetLastError();
 }
 
@@ -1230,8 +1217,9 @@ CGS_EXPORT int cgs_flash_attn_fwd(const void* q, const void* k, const void* v, v
                                   long long ksh, long long vsb, long long vss, long long vsh, long long osb,
                                   long long oss, long long osh, float scale, const void* key_mask, int causal,
                                   hipStream_t stream) {
-  return flash_attn_impl(q, k, v, o, B, H, Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, scale,
-                         key_mask, causal, nullptr, stream);
+  const AttnArgs a{q, k, v, o, B, H, Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, scale,
+                   key_mask, causal, nullptr, stream};
+  return flash_attn_dispatch(a, g_attn_variant);
 }
 
 // Same, plus the per-(b, h, query) natural-log LSE of the scaled scores (fp32 [B, H, Sq]) for
@@ -1241,6 +1229,7 @@ CGS_EXPORT int cgs_flash_attn_fwd_lse(const void* q, const void* k, const void* 
                                       long long kss, long long ksh, long long vsb, long long vss, long long vsh,
                                       long long osb, long long oss, long long osh, float scale, hipStream_t stream) {
   if (!lse) return (int)hipErrorInvalidValue;
-  return flash_attn_impl(q, k, v, o, B, H, Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, scale,
-                         nullptr, 0, lse, stream);
+  const AttnArgs a{q, k, v, o, B, H, Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, scale,
+                   nullptr, 0, lse, stream};
+  return flash_attn_dispatch(a, g_attn_variant);
 }

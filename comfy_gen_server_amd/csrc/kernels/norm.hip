@@ -370,37 +370,46 @@ static int gn_slices(int C) {
   return best;
 }
 
-// x, y: [N, HW, C] (NHWC); gamma/beta [C] in the activation dtype; pre_add [N, C] (act dtype) or null.
+// The statistics kernel for slices of nch 16-byte chunks: the pixel-packed forms up to 32 chunks, else KM = 1..4
+// chunk rounds per lane.
+using GnPartialKernel = decltype(&gn_partial_kernel<CGS_BF16, 1>);
+template <int DT>
+static GnPartialKernel gn_partial_kernel_for(int nch) {
+  if (nch <= 8) return gn_partial_kernel<DT, 1, 8>;
+  if (nch <= 16) return gn_partial_kernel<DT, 1, 4>;
+  if (nch <= 32) return gn_partial_kernel<DT, 1, 2>;
+  if (nch <= 64) return gn_partial_kernel<DT, 1>;
+  if (nch <= 128) return gn_partial_kernel<DT, 2>;
+  if (nch <= 192) return gn_partial_kernel<DT, 3>;
+  return gn_partial_kernel<DT, 4>;
+}
+
+// The statistics pass of both GroupNorm forms: x ([N, HW, C1]) / x2 ([N, HW, C - C1], or null: C1 = C) -> part, the
+// per-(n, block, c) (mean, M2) partials of *nb blocks of *ppb pixels (what the finalize pass walks).
+static int gn_partial_launch(const void* x, const void* x2, int C1, float* part, int N, int HW, int C, int G, int dtype,
+                             hipStream_t stream, int* ppb, int* nb) {
+  const int ns = gn_slices(C);      // equal, 8-aligned channel slices
+  if (C % 8 || C % G || C % (8 * ns) || C > 8192 || C1 % 8 || C1 > C) return (int)hipErrorInvalidValue;
+  const int CS = C / ns;
+  *ppb = gn_pix_per_block(N, HW);
+  *nb = (HW + *ppb - 1) / *ppb;
+  const GnPartialKernel kern =
+      dtype == CGS_BF16 ? gn_partial_kernel_for<CGS_BF16>(CS / 8) : gn_partial_kernel_for<CGS_F16>(CS / 8);
+  kern<<<dim3(*nb, N, ns), GN_THREADS, 8 * CS * sizeof(float), stream>>>((const u16*)x, (const u16*)x2, C1, part, HW, C,
+                                                                         *ppb, *nb, CS);
+  return 0;
+}
+
+// x, y: [N, HW, C] (NHWC); gamma/beta [C] in the activation dtype; pre_add [N, C] (act dtype, row stride pld) or null.
 // ws: workspace of cgs_groupnorm_workspace() bytes (torch-allocated so it is graph-capturable).
 static int groupnorm_impl(const void* x, const void* x2, int C1, void* y, const void* gamma, const void* beta,
                           const void* pre_add, void* ws, int N, int HW, int C, int G, float eps, int silu, int dtype,
                           hipStream_t stream, int pld) {
-  const int ns = gn_slices(C);      // equal, 8-aligned channel slices
-  if (C % 8 || C % G || C % (8 * ns) || C > 8192 || C1 % 8 || C1 > C) return (int)hipErrorInvalidValue;
-  const int CS = C / ns;
-  int ppb = gn_pix_per_block(N, HW);
-  int nb = (HW + ppb - 1) / ppb;
+  if (pre_add && pld < C) return (int)hipErrorInvalidValue;
+  int ppb, nb;
   float* part = (float*)ws;
+  if (const int rc = gn_partial_launch(x, x2, C1, part, N, HW, C, G, dtype, stream, &ppb, &nb)) return rc;
   float* ab = part + (size_t)N * nb * C * 2;
-  dim3 g1(nb, N, ns);
-  const int km = (CS / 8 + 63) / 64;  // 1..4
-#define CGS_GN_PARTIAL(KMV)                                                                                     \
-  if (dtype == CGS_BF16)                                                                                        \
-    gn_partial_kernel<CGS_BF16, KMV><<<g1, GN_THREADS, 8 * CS * sizeof(float), stream>>>((const u16*)x, (const u16*)x2, C1, part, HW, C, ppb, nb, CS); \
-  else                                                                                                          \
-    gn_partial_kernel<CGS_F16, KMV><<<g1, GN_THREADS, 8 * CS * sizeof(float), stream>>>((const u16*)x, (const u16*)x2, C1, part, HW, C, ppb, nb, CS);
-#define CGS_GN_PARTIAL_PK(PKV)                                                                                  \
-  if (dtype == CGS_BF16)                                                                                        \
-    gn_partial_kernel<CGS_BF16, 1, PKV><<<g1, GN_THREADS, 8 * CS * sizeof(float), stream>>>((const u16*)x, (const u16*)x2, C1, part, HW, C, ppb, nb, CS); \
-  else                                                                                                          \
-    gn_partial_kernel<CGS_F16, 1, PKV><<<g1, GN_THREADS, 8 * CS * sizeof(float), stream>>>((const u16*)x, (const u16*)x2, C1, part, HW, C, ppb, nb, CS);
-  const int nch = CS / 8;
-  if (nch <= 8) { CGS_GN_PARTIAL_PK(8) }
-  else if (nch <= 16) { CGS_GN_PARTIAL_PK(4) }
-  else if (nch <= 32) { CGS_GN_PARTIAL_PK(2) }
-  else if (km == 1) { CGS_GN_PARTIAL(1) } else if (km == 2) { CGS_GN_PARTIAL(2) } else if (km == 3) { CGS_GN_PARTIAL(3) } else { CGS_GN_PARTIAL(4) }
-#undef CGS_GN_PARTIAL
-#undef CGS_GN_PARTIAL_PK
   gn_finalize_kernel<<<dim3(G, N), 256, 0, stream>>>(part, gamma, beta, pre_add, ab, HW, C, G, ppb, nb, eps, dtype,
                                                     pld);
   return gn_apply_launch(x, x2, C1, y, ab, N, HW, C, silu, dtype, stream);
@@ -409,26 +418,9 @@ static int groupnorm_impl(const void* x, const void* x2, int C1, void* y, const 
 // The statistics half of groupnorm_impl: per-(n, g) (mean, M2) of the given rows into stats [N][G][2].
 static int groupnorm_stats_impl(const void* x, const void* x2, int C1, const void* pre_add, void* ws, float* stats,
                                 int N, int HW, int C, int G, int dtype, hipStream_t stream) {
-  const int ns = gn_slices(C);
-  if (C % 8 || C % G || C % (8 * ns) || C > 8192 || C1 % 8 || C1 > C) return (int)hipErrorInvalidValue;
-  const int CS = C / ns;
-  int ppb = gn_pix_per_block(N, HW);
-  int nb = (HW + ppb - 1) / ppb;
+  int ppb, nb;
   float* part = (float*)ws;
-  dim3 g1(nb, N, ns);
-  const int km = (CS / 8 + 63) / 64;
-  const int nch = CS / 8;
-#define CGS_GN_PARTIAL(KMV, PKV)                                                                                \
-  if (dtype == CGS_BF16)                                                                                        \
-    gn_partial_kernel<CGS_BF16, KMV, PKV><<<g1, GN_THREADS, 8 * CS * sizeof(float), stream>>>((const u16*)x, (const u16*)x2, C1, part, HW, C, ppb, nb, CS); \
-  else                                                                                                          \
-    gn_partial_kernel<CGS_F16, KMV, PKV><<<g1, GN_THREADS, 8 * CS * sizeof(float), stream>>>((const u16*)x, (const u16*)x2, C1, part, HW, C, ppb, nb, CS);
-  if (nch <= 8) { CGS_GN_PARTIAL(1, 8) }
-  else if (nch <= 16) { CGS_GN_PARTIAL(1, 4) }
-  else if (nch <= 32) { CGS_GN_PARTIAL(1, 2) }
-  else if (km == 1) { CGS_GN_PARTIAL(1, 1) } else if (km == 2) { CGS_GN_PARTIAL(2, 1) }
-  else if (km == 3) { CGS_GN_PARTIAL(3, 1) } else { CGS_GN_PARTIAL(4, 1) }
-#undef CGS_GN_PARTIAL
+  if (const int rc = gn_partial_launch(x, x2, C1, part, N, HW, C, G, dtype, stream, &ppb, &nb)) return rc;
   gn_finalize_kernel<true><<<dim3(G, N), 256, 0, stream>>>(part, nullptr, nullptr, pre_add, stats, HW, C, G, ppb, nb,
                                                           0.f, dtype, C);
   return (int)hipGetLastError();
@@ -496,13 +488,20 @@ static int gn_apply_launch(const void* x, const void* x2, int C1, void* y, const
 
 // GroupNorm whose statistics pass already ran in the producer's epilogue (cgs_conv2d_nhwc_gns): part =
 // [N, HW / ppb, C] (mean, M2) partials of ppb pixels each; only finalize + apply run. ab: N * C * 2 floats.
+static int groupnorm_part_impl(const void* x, void* y, const void* gamma, const void* beta, const void* pre_add,
+                               int pld, const float* part, float* ab, int N, int HW, int C, int G, int ppb, float eps,
+                               int silu, int dtype, hipStream_t stream) {
+  if (C % 8 || C % G || ppb <= 0 || HW % ppb || !part || !ab || (pre_add && pld < C)) return (int)hipErrorInvalidValue;
+  const int nb = HW / ppb;
+  gn_finalize_kernel<<<dim3(G, N), 256, 0, stream>>>(part, gamma, beta, pre_add, ab, HW, C, G, ppb, nb, eps, dtype,
+                                                    pld);
+  return gn_apply_launch(x, nullptr, C, y, ab, N, HW, C, silu, dtype, stream);
+}
+
 CGS_EXPORT int cgs_groupnorm_nhwc_part(const void* x, void* y, const void* gamma, const void* beta, const void* pre_add,
                                        const float* part, float* ab, int N, int HW, int C, int G, int ppb, float eps,
                                        int silu, int dtype, hipStream_t stream) {
-  if (C % 8 || C % G || ppb <= 0 || HW % ppb || !part || !ab) return (int)hipErrorInvalidValue;
-  const int nb = HW / ppb;
-  gn_finalize_kernel<<<dim3(G, N), 256, 0, stream>>>(part, gamma, beta, pre_add, ab, HW, C, G, ppb, nb, eps, dtype, C);
-  return gn_apply_launch(x, nullptr, C, y, ab, N, HW, C, silu, dtype, stream);
+  return groupnorm_part_impl(x, y, gamma, beta, pre_add, C, part, ab, N, HW, C, G, ppb, eps, silu, dtype, stream);
 }
 
 CGS_EXPORT int cgs_groupnorm_nhwc_ws(const void* x, void* y, const void* gamma, const void* beta, const void* pre_add,
@@ -524,25 +523,19 @@ CGS_EXPORT int cgs_groupnorm_nhwc_dual(const void* x, const void* x2, int C1, vo
 CGS_EXPORT int cgs_groupnorm_nhwc_ws_pld(const void* x, void* y, const void* gamma, const void* beta,
                                          const void* pre_add, int pld, void* ws, int N, int HW, int C, int G, float eps,
                                          int silu, int dtype, hipStream_t stream) {
-  if (pre_add && pld < C) return (int)hipErrorInvalidValue;
   return groupnorm_impl(x, nullptr, C, y, gamma, beta, pre_add, ws, N, HW, C, G, eps, silu, dtype, stream, pld);
 }
 
 CGS_EXPORT int cgs_groupnorm_nhwc_dual_pld(const void* x, const void* x2, int C1, void* y, const void* gamma,
                                            const void* beta, const void* pre_add, int pld, void* ws, int N, int HW,
                                            int C, int G, float eps, int silu, int dtype, hipStream_t stream) {
-  if (pre_add && pld < C) return (int)hipErrorInvalidValue;
   return groupnorm_impl(x, x2, C1, y, gamma, beta, pre_add, ws, N, HW, C, G, eps, silu, dtype, stream, pld);
 }
 
 CGS_EXPORT int cgs_groupnorm_nhwc_part_pld(const void* x, void* y, const void* gamma, const void* beta,
                                            const void* pre_add, int pld, const float* part, float* ab, int N, int HW,
                                            int C, int G, int ppb, float eps, int silu, int dtype, hipStream_t stream) {
-  if (C % 8 || C % G || ppb <= 0 || HW % ppb || !part || !ab || (pre_add && pld < C)) return (int)hipErrorInvalidValue;
-  const int nb = HW / ppb;
-  gn_finalize_kernel<<<dim3(G, N), 256, 0, stream>>>(part, gamma, beta, pre_add, ab, HW, C, G, ppb, nb, eps, dtype,
-                                                    pld);
-  return gn_apply_launch(x, nullptr, C, y, ab, N, HW, C, silu, dtype, stream);
+  return groupnorm_part_impl(x, y, gamma, beta, pre_add, pld, part, ab, N, HW, C, G, ppb, eps, silu, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -379,6 +379,16 @@ _FLASH_HEAD_DIMS = (32, 40, 64, 80, 96, 128, 160)
 _ATTN_ALLOW_LIB = os.environ.get("CGS_ATTN_ALLOW_LIB", "0") == "1"
 
 
+def _attn_operands(q, k, v, o, heads):
+    """``(q, k, v, o, B, H, Sq, Sk, D, twelve element strides)``: the argument prefix of cgs_flash_attn_fwd / _v (and,
+    with lse after o, _lse) for token-major [B, S, H * D] operands, head stride D."""
+    B, Sq, HD = q.shape
+    D = HD // heads
+    return (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), B, heads, Sq, k.shape[1], D,
+            q.stride(0), q.stride(1), D, k.stride(0), k.stride(1), D, v.stride(0), v.stride(1), D,
+            o.stride(0), o.stride(1), D)
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
               mask: torch.Tensor | None = None, causal: bool = False,
               key_padding: torch.Tensor | None = None) -> torch.Tensor:
@@ -411,12 +421,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
 
         def run_hip():
             o = torch.empty((B, Sq, HD), device=q.device, dtype=q.dtype)
-            _check(_lib().cgs_flash_attn_fwd(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                B, heads, Sq, Sk, D,
-                q.stride(0), q.stride(1), D, k.stride(0), k.stride(1), D, v.stride(0), v.stride(1), D,
-                o.stride(0), o.stride(1), D,
-                1.0 / math.sqrt(D), _ptr(kp), 1 if causal else 0, _stream()), "cgs_flash_attn_fwd")
+            _check(_lib().cgs_flash_attn_fwd(*_attn_operands(q, k, v, o, heads), 1.0 / math.sqrt(D), _ptr(kp),
+                                             1 if causal else 0, _stream()), "cgs_flash_attn_fwd")
             return o
 
         if (wide_ok and heads == 1 and _WIDE_MAT and kp is None and Sk % 64 == 0 and Sk <= 16384
@@ -432,10 +438,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
                 and B * heads * Sq * Sk >= (1 << 22) and _native.has_kernel("cgs_flash_attn_fwd_v")):
             def run_v(var):
                 o = torch.empty((B, Sq, HD), device=q.device, dtype=q.dtype)
-                _check(_lib().cgs_flash_attn_fwd_v(
-                    q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), B, heads, Sq, Sk, D,
-                    q.stride(0), q.stride(1), D, k.stride(0), k.stride(1), D, v.stride(0), v.stride(1), D,
-                    o.stride(0), o.stride(1), D, 1.0 / math.sqrt(D), var, _stream()), "cgs_flash_attn_fwd_v")
+                _check(_lib().cgs_flash_attn_fwd_v(*_attn_operands(q, k, v, o, heads), 1.0 / math.sqrt(D), var,
+                                                   _stream()), "cgs_flash_attn_fwd_v")
                 return o
             def run_ks(ks):
                 o = torch.empty((B, Sq, HD), device=q.device, dtype=q.dtype)
@@ -575,10 +579,9 @@ def attention_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int)
         o = torch.empty((B, Sq, HD), device=q.device, dtype=q.dtype)
         lse = torch.empty((B, heads, Sq), device=q.device, dtype=torch.float32)
         count("attention", "hip")
-        _check(_lib().cgs_flash_attn_fwd_lse(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, heads, Sq, Sk, D,
-            q.stride(0), q.stride(1), D, k.stride(0), k.stride(1), D, v.stride(0), v.stride(1), D,
-            o.stride(0), o.stride(1), D, 1.0 / math.sqrt(D), _stream()), "cgs_flash_attn_fwd_lse")
+        pre = _attn_operands(q, k, v, o, heads)
+        _check(_lib().cgs_flash_attn_fwd_lse(*pre[:4], lse.data_ptr(), *pre[4:], 1.0 / math.sqrt(D), _stream()),
+               "cgs_flash_attn_fwd_lse")
         return o, lse
     if q.device.type != "cpu":
         vendor_fallback("attention", f"LSE form: dtype {q.dtype}, head dim {D}")
@@ -774,52 +777,28 @@ def group_norm(x: torch.Tensor, groups: int, weight: torch.Tensor | None, bias: 
             # a [N, C] column slice of a wider row-major tensor (the UNet's batched time-embedding projection)
             # is read in place through a row stride; anything else is made contiguous
             if not (pa.dim() == 2 and pa.shape == (N, C) and pa.stride(1) == 1 and pa.stride(0) >= C
-                    and _native.has_kernel("cgs_groupnorm_nhwc_ws_pld")):
+                    and _native.has_kernel("cgs_groupnorm_nhwc_dual_pld")):
                 pa = pa.contiguous()
             pld = pa.stride(0) if pa.dim() == 2 and N > 1 else C
-        strided = pa is not None and pld != C
+        # the _pld entries take every form: pld = C for a contiguous (or no) pre-add, a null x2 with C1 = C for
+        # one source
         gp = getattr(x, "_cgs_gnpart", None) if x2 is None else None
         if gp is not None and gp[1] == x.data_ptr() and xc is x and gp[0].numel() == N * (H * W // 64) * C * 2 \
-                and _native.has_kernel("cgs_groupnorm_nhwc_part"):
+                and _native.has_kernel("cgs_groupnorm_nhwc_part_pld"):
             # statistics from the producing conv's epilogue (conv2d(gn_stats=True)): finalize + apply only
             ab = torch.empty(N * C * 2, device=x.device, dtype=torch.float32)
-            if strided:
-                _check(_lib().cgs_groupnorm_nhwc_part_pld(xc.data_ptr(), y.data_ptr(), weight.data_ptr(), _ptr(bias),
-                                                          pa.data_ptr(), pld, gp[0].data_ptr(), ab.data_ptr(), N,
-                                                          H * W, C, groups, 64, float(eps), 1 if silu else 0,
-                                                          _DT[x.dtype], _stream()), "cgs_groupnorm_nhwc_part_pld")
-            else:
-                _check(_lib().cgs_groupnorm_nhwc_part(xc.data_ptr(), y.data_ptr(), weight.data_ptr(), _ptr(bias),
-                                                      _ptr(pa), gp[0].data_ptr(), ab.data_ptr(), N, H * W, C, groups,
-                                                      64, float(eps), 1 if silu else 0, _DT[x.dtype], _stream()),
-                       "cgs_groupnorm_nhwc_part")
+            _check(_lib().cgs_groupnorm_nhwc_part_pld(xc.data_ptr(), y.data_ptr(), weight.data_ptr(), _ptr(bias),
+                                                      _ptr(pa), pld, gp[0].data_ptr(), ab.data_ptr(), N, H * W, C,
+                                                      groups, 64, float(eps), 1 if silu else 0, _DT[x.dtype],
+                                                      _stream()), "cgs_groupnorm_nhwc_part_pld")
             return y
         wsb = int(_lib().cgs_groupnorm_workspace(N, H * W, C))
         ws = torch.empty((wsb + 3) // 4, device=x.device, dtype=torch.float32)
-        if x2 is None:
-            if strided:
-                _check(_lib().cgs_groupnorm_nhwc_ws_pld(xc.data_ptr(), y.data_ptr(), weight.data_ptr(), _ptr(bias),
-                                                        pa.data_ptr(), pld, ws.data_ptr(), N, H * W, C, groups,
-                                                        float(eps), 1 if silu else 0, _DT[x.dtype], _stream()),
-                       "cgs_groupnorm_nhwc_ws_pld")
-            else:
-                _check(_lib().cgs_groupnorm_nhwc_ws(xc.data_ptr(), y.data_ptr(), weight.data_ptr(),
-                                                    _ptr(bias), _ptr(pa), ws.data_ptr(), N, H * W, C, groups,
-                                                    float(eps), 1 if silu else 0, _DT[x.dtype], _stream()),
-                       "cgs_groupnorm_nhwc_ws")
-        else:
-            x2c = x2.contiguous(memory_format=torch.channels_last)
-            if strided:
-                _check(_lib().cgs_groupnorm_nhwc_dual_pld(xc.data_ptr(), x2c.data_ptr(), C1, y.data_ptr(),
-                                                          weight.data_ptr(), _ptr(bias), pa.data_ptr(), pld,
-                                                          ws.data_ptr(), N, H * W, C, groups, float(eps),
-                                                          1 if silu else 0, _DT[x.dtype], _stream()),
-                       "cgs_groupnorm_nhwc_dual_pld")
-            else:
-                _check(_lib().cgs_groupnorm_nhwc_dual(xc.data_ptr(), x2c.data_ptr(), C1, y.data_ptr(),
-                                                      weight.data_ptr(), _ptr(bias), _ptr(pa), ws.data_ptr(), N, H * W,
-                                                      C, groups, float(eps), 1 if silu else 0, _DT[x.dtype],
-                                                      _stream()), "cgs_groupnorm_nhwc_dual")
+        x2c = None if x2 is None else x2.contiguous(memory_format=torch.channels_last)
+        _check(_lib().cgs_groupnorm_nhwc_dual_pld(xc.data_ptr(), _ptr(x2c), C1, y.data_ptr(), weight.data_ptr(),
+                                                  _ptr(bias), _ptr(pa), pld, ws.data_ptr(), N, H * W, C, groups,
+                                                  float(eps), 1 if silu else 0, _DT[x.dtype], _stream()),
+               "cgs_groupnorm_nhwc_dual_pld")
         return y
     if x2 is not None:
         x = torch.cat([x, x2], dim=1)

@@ -1,13 +1,14 @@
 """Per-element error bounds (tests/_bounds.py) on the device for the bf16 GEMM, conv and attention kernels.
 
 Every case names one kernel and a shape inside that kernel's own dispatch domain, so the kernel of the test id is
-the one that runs (gemm_dispatch / conv_launch / flash_attn_impl fall through to another kernel outside it; no
+the one that runs (gemm_dispatch / conv_launch / flash_attn_dispatch fall through to another kernel outside it; no
 case relies on that). References are fp64 on the device. The shapes are the smallest that reach an edge: a single
 partial tile, one row / one 8-wide vector past a full tile, the minimum K, an odd number of K steps, more tiles
 than a persistent kernel's workgroups, the workspace (split-K) paths. The guard tests place C with ldc = N + 8 in
 the middle of a pattern-filled buffer and require every element outside [0, M) x [0, N) to keep its bits; their
 four row strides all differ (lda = K + 8, ldw = K + 16, ldc = N + 8, ldr = N + 16, every operand a view of a wider
-allocation), so a launcher that swaps two of them misses the bound."""
+allocation), so a launcher that swaps two of them misses the bound; test_attention_bound_distinct_strides does the
+same for the attention entries' twelve strides."""
 import math
 
 import pytest
@@ -512,7 +513,7 @@ def test_conv_bound_v7_split_tail(cuda, C1, C2, s, up):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-# flash_attn_impl (csrc/kernels/attention.hip): variant 1 = the generic kernel (every head dim, causal, key mask);
+# flash_attn_dispatch (csrc/kernels/attention.hip): variant 1 = the generic kernel (every head dim, causal, key mask);
 # 2 / 4 = the D = 64 kernel on 256-row query blocks, 5 on 128-row blocks, 3 = the short-KV kernel (D = 64,
 # Sk <= 128); 2 .. 5 take neither mask. D = 512 has its own kernel whatever the variant.
 SQS, SKS = (1, 63, 129, 257), (1, 4, 63, 65, 130)
@@ -610,6 +611,104 @@ def test_attention_bound_causal_and_key_padding(cuda, attn_variant, D):
                       f"attention/generic key_padding D={D} Sq={Sq} Sk={Sk}")
 
 
+def _padded(t, rows, cols):
+    """t [B, S, C] as the corner view of a [B, S + rows, C + cols] buffer: its own batch and row stride."""
+    B, S, C = t.shape
+    buf = torch.zeros(B, S + rows, C + cols, device=t.device, dtype=t.dtype)
+    buf[:, :S, :C] = t
+    return buf[:, :S, :C]
+
+
+def _distinct_mult8(strides):
+    return len(set(strides)) == len(strides) and all(s % 8 == 0 for s in strides)
+
+
+def _bshd_strides(*ts):
+    """(batch, token, head) element strides of [B, S, H, D] views, in the order the library entries take them."""
+    return [t.stride(i) for t in ts for i in (0, 1, 2)]
+
+
+def _stride_views(cuda, B, H, Sq, Sk, D, seed):
+    """q, k, v, o as [B, S, H, D] views of four differently padded buffers, and o's buffer. q: token-major in
+    [B, Sq + 1, H D + 8]; k: head-major in [B, H, Sk + 2, D + 8]; v: token-major in [B, Sk + 3, H (D + 24)] (the
+    24 elements of padding per head, not per row: with them at the end of the row v's head stride would be D like
+    q's, and two equal strides can be swapped unseen); o: head-major in [B, H, Sq + 1, D + 16], filled with SENTINEL."""
+    torch.manual_seed(seed)
+    q = torch.randn(B, Sq + 1, H * D + 8, device=cuda).to(BF)[:, :Sq, :H * D].unflatten(2, (H, D))
+    k = torch.randn(B, H, Sk + 2, D + 8, device=cuda).to(BF)[:, :, :Sk, :D].transpose(1, 2)
+    v = torch.randn(B, Sk + 3, H, D + 24, device=cuda).to(BF)[:, :Sk, :, :D]
+    ob = torch.full((B, H, Sq + 1, D + 16), SENTINEL, device=cuda, dtype=BF)
+    return q, k, v, ob[:, :, :Sq, :D].transpose(1, 2), ob
+
+
+SENTINEL = -8192.0
+
+
+def _flash(lib, entry, q, k, v, o, *tail, lse=None):
+    """cgs_flash_attn_fwd (tail: key_mask, causal), _v (tail: variant) or _lse on [B, S, H, D] views."""
+    B, Sq, H, D = q.shape
+    args = [q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()] + ([] if lse is None else [lse.data_ptr()])
+    args += [B, H, Sq, k.shape[1], D] + _bshd_strides(q, k, v, o) + [1.0 / math.sqrt(D)] + list(tail)
+    return getattr(lib, entry)(*args, core._stream())
+
+
+def _stride_cases():
+    cases = [("v1", 3, D, Sq, Sk) for D in (40, 64) for Sq, Sk in ((63, 65), (257, 130))]     # generic kernel
+    cases += [(f"v{var}", 3, 64, Sq, Sk) for var in (2, 5) for Sq, Sk in ((63, 65), (257, 130))]
+    cases += [("v3", 3, 64, Sq, Sk) for Sq, Sk in ((129, 63), (257, 128))]                    # short-KV
+    cases += [("wide", 2, 512, Sq, Sk) for Sq, Sk in ((63, 65), (33, 130))]
+    cases += [("lse", 3, D, 257, 130) for D in (64, 40)]                                      # fast / generic kernel
+    return cases
+
+
+@pytest.mark.parametrize("form,H,D,Sq,Sk", _stride_cases())
+def test_attention_bound_distinct_strides(cuda, form, H, D, Sq, Sk):
+    """The library called directly with twelve pairwise distinct strides (every other attention case gives q, k and
+    v the same row and batch strides, head stride D and a contiguous output): a launcher that swaps two of them
+    misses the bound or writes outside o's view."""
+    lib = _native.load_kernels()
+    B = 2
+    q, k, v, o, ob = _stride_views(cuda, B, H, Sq, Sk, D, seed=Sq * 1000 + Sk + D)
+    strides = _bshd_strides(q, k, v, o)
+    assert _distinct_mult8(strides), strides
+    lse = torch.empty(B, H, Sq, device=cuda, dtype=torch.float32) if form == "lse" else None
+    if form == "lse":
+        rc = _flash(lib, "cgs_flash_attn_fwd_lse", q, k, v, o, lse=lse)
+    elif form == "wide":
+        rc = _flash(lib, "cgs_flash_attn_fwd", q, k, v, o, None, 0)
+    else:
+        rc = _flash(lib, "cgs_flash_attn_fwd_v", q, k, v, o, int(form[1]))
+    assert rc == 0
+    qc, kc, vc = (t.reshape(B, t.shape[1], H * D) for t in (q, k, v))                       # contiguous copies
+    ref, tol = attention_bound(qc, kc, vc, H)
+    assert_within(o.reshape(B, Sq, H * D), ref, tol, f"attention/{form} distinct strides D={D} Sq={Sq} Sk={Sk}")
+    outside = torch.ones_like(ob, dtype=torch.bool)
+    outside[:, :, :Sq, :D] = False
+    assert bool((ob[outside] == SENTINEL).all())
+    if form == "lse":
+        s = (qc.float().view(B, Sq, H, D).transpose(1, 2) @ kc.float().view(B, Sk, H, D).permute(0, 2, 3, 1)) * D ** -0.5
+        assert (lse - torch.logsumexp(s, -1)).abs().max().item() < 2e-2
+
+
+def test_attention_variant_call_leaves_process_setting(cuda):
+    """cgs_flash_attn_fwd_v picks its kernel per call: it neither reads nor changes the cgs_attn_set_variant
+    setting (one thread; the generic and the D = 64 kernel do not round alike, so a leaked variant shows)."""
+    lib = _native.load_kernels()
+    B, H, Sq, Sk, D = 2, 3, 257, 130, 64
+    q, k, v = (t.unflatten(2, (H, D)) for t in _qkv(cuda, B, H, Sq, Sk, D, seed=5))
+    o1, ov, o2 = (torch.empty_like(q) for _ in range(3))
+    lib.cgs_attn_set_variant(1)
+    try:
+        assert _flash(lib, "cgs_flash_attn_fwd", q, k, v, o1, None, 0) == 0
+        assert _flash(lib, "cgs_flash_attn_fwd_v", q, k, v, ov, 2) == 0
+        assert _flash(lib, "cgs_flash_attn_fwd", q, k, v, o2, None, 0) == 0
+    finally:
+        lib.cgs_attn_set_variant(0)
+    assert torch.equal(o1, o2)
+    ref, tol = attention_bound(q.flatten(2), k.flatten(2), v.flatten(2), H)
+    assert_within(ov.flatten(2), ref, tol, "attention/d64fast per call under process variant 1")
+
+
 @pytest.mark.parametrize("rows", [128, 256])
 def test_attention_bound_kv2(cuda, rows, monkeypatch):
     lib = _native.load_kernels()
@@ -619,10 +718,10 @@ def test_attention_bound_kv2(cuda, rows, monkeypatch):
     try:
         for Sq, S2 in ((1, 1), (63, 4), (129, 65), (257, 130)):
             torch.manual_seed(Sq)
-            qkv = torch.randn(2, Sq, 3 * C, device=cuda).to(BF)
-            kv2 = torch.randn(2, S2, 2 * C, device=cuda).to(BF)
-            q, k1, v1 = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-            k2, v2 = kv2[..., :C], kv2[..., C:]
+            # q and the four sources each in a padded buffer of its own: ten different strides
+            q, k1, v1 = (_padded(torch.randn(2, Sq, C, device=cuda).to(BF), i, 8 * i) for i in (1, 2, 3))
+            k2, v2 = (_padded(torch.randn(2, S2, C, device=cuda).to(BF), i, 8 * i) for i in (4, 5))
+            assert _distinct_mult8([t.stride(i) for t in (q, k1, v1, k2, v2) for i in (0, 1)])
             rcs = []
             with monkeypatch.context() as mp:
                 mp.setattr(lib, "cgs_flash_attn_fwd_kv2", lambda *a: rcs.append(real(*a)) or rcs[-1])
@@ -643,8 +742,9 @@ def test_attention_bound_key_split(cuda, ks, Sk):
     assert tiles == 4 * ks and (ks - 1) * ((tiles + ks - 1) // ks) * 64 < Sk and (Sk - 1 + 63) // 64 < 4 * ks
     B, H, D = 2, 3, 64
     for Sq, spike in ((257, False), (63, True)):
-        q, k, v = _qkv(cuda, B, H, Sq, Sk, D, seed=Sk + Sq, spike=spike)
-        o = torch.empty_like(q)
+        q, k, v = (_padded(t, i, 8 * i) for i, t in enumerate(_qkv(cuda, B, H, Sq, Sk, D, seed=Sk + Sq, spike=spike), 1))
+        o = _padded(torch.empty(B, Sq, H * D, device=cuda, dtype=BF), 4, 32)
+        assert _distinct_mult8([t.stride(i) for t in (q, k, v, o) for i in (0, 1)])
         ws_o = torch.empty(ks * B * Sq * H * D, device=cuda, dtype=BF)
         ws_l = torch.empty(ks * B * H * Sq, device=cuda, dtype=torch.float32)
         assert lib.cgs_flash_attn_fwd_ks(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), B, H, Sq, Sk,
