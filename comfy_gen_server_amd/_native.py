@@ -88,6 +88,10 @@ KERNEL_SIGNATURES = {
     # mask, nW, hscale [H] fp32 or null, stream
     "cgs_flash_attn_fwd_bias": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
                                 _F, _P, _P, _I, _P, _P],
+    # generic kernel + additive score mask by strides (ops.attention(mask=...)): ..., scale, mask, kind (1 fp32,
+    # 2 bf16), mask strides (b, h, q; elements, 0 broadcasts), key_mask, causal, stream
+    "cgs_flash_attn_fwd_mask": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
+                                _F, _P, _I, _L, _L, _L, _P, _I, _P],
     # same + fp32 LSE [B, H, Sq] out (ring attention merge): q,k,v,o,lse, B,H,Sq,Sk,D, 12 strides, scale
     "cgs_flash_attn_fwd_lse": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
                                _F, _P],

@@ -14,6 +14,7 @@
 //    ds_read_b64_tr_b16 hardware-transposed LDS reads.
 //  * exp2 with log2(e) folded into the score scale; fully-masked rows stay finite.
 #include "common.h"
+#include <type_traits>
 
 #define ATT_KV 64
 #define ATT_WAVES 4
@@ -32,14 +33,28 @@ struct AttnBias {
   int nW;
 };
 
-template <int DP, bool BIAS = false>
+// Additive score mask of the token-major op (ops.attention(mask=...)): element (b, h, q, key) is at
+// p[b * sb + h * sh + q * sq + key], element strides, 0 broadcasts that dimension; fp32 (ATT_MASK_F32) or bf16
+// (ATT_MASK_BF16) values, -inf blocks a key. A lane reads its query's row in runs of 4 consecutive keys as one
+// 8-B / 16-B vector, so p and every non-zero stride are multiples of 4 elements: the launcher refuses anything
+// else, and the op copies such a mask (Sk = 77 rows, a column slice) at its own, unexpanded shape with the key
+// dimension padded to a multiple of 8 -- the kernel has no scalar path for unaligned rows.
+#define ATT_MASK_NONE 0
+#define ATT_MASK_F32 1
+#define ATT_MASK_BF16 2
+struct AttnMask {
+  const void* p;
+  long long sb, sh, sq;
+};
+
+template <int DP, bool BIAS = false, int MK = ATT_MASK_NONE>
 __global__ __launch_bounds__(256, (DP >= 160 ? 1 : 2)) void flash_fwd_kernel(
     const u16* __restrict__ qp, const u16* __restrict__ kp, const u16* __restrict__ vp, u16* __restrict__ op,
     int B, int H, int Sq, int Sk, int D,
     long long qsb, long long qss, long long qsh, long long ksb, long long kss, long long ksh,
     long long vsb, long long vss, long long vsh, long long osb, long long oss, long long osh,
     float scale_log2, const signed char* __restrict__ key_mask, int causal, int nqb, float* __restrict__ lse,
-    AttnBias ab = AttnBias{nullptr, nullptr, nullptr, 1}) {
+    AttnBias ab = AttnBias{nullptr, nullptr, nullptr, 1}, AttnMask am = AttnMask{nullptr, 0, 0, 0}) {
   constexpr int KS = DP / 16;        // k-steps of the QK product
   constexpr int NDT = DP / 32;       // 32-wide d tiles of the output
   constexpr int LDW = DP + 8;        // padded LDS row (elements)
@@ -122,12 +137,72 @@ __global__ __launch_bounds__(256, (DP >= 160 ? 1 : 2)) void flash_fwd_kernel(
     }
   };
 
+  // ---- mask: the lane's 32 scores of a tile are 8 runs of 4 consecutive keys (run 4 * kt + (r >> 2) starts at key
+  // t * 64 + 32 * kt + 8 * (r >> 2) + 4 * hf), each loaded as one vector. All 8 are issued before the tile's QK^T
+  // MFMAs, next to load_tile(t + 1). Rows >= Sq read the last row. In a partial last tile a run that crosses Sk is
+  // read element by element up to Sk - 1 and a run past Sk is not read: nothing past the end of a mask row is
+  // touched.
+  using MaskVec = std::conditional_t<MK == ATT_MASK_F32, f32x4, s16x4>;
+  using MaskElt = std::conditional_t<MK == ATT_MASK_F32, float, short>;
+  MaskVec mreg[MK == ATT_MASK_NONE ? 1 : 8];
+  const MaskElt* mrow = nullptr;
+  if constexpr (MK != ATT_MASK_NONE)
+    mrow = static_cast<const MaskElt*>(am.p) + b * am.sb + h * am.sh + (long long)min(q_row, Sq - 1) * am.sq;
+  auto load_mask = [&](int t, int kt) {
+    const int k0 = t * ATT_KV + kt * 32 + 4 * hf;
+    if (t * ATT_KV + ATT_KV <= Sk) {   // wave-uniform: every tile but a partial last one
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        mreg[kt * 4 + i] = *reinterpret_cast<const MaskVec*>(mrow + k0 + 8 * i);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key0 = k0 + 8 * i;
+        MaskVec m = {0, 0, 0, 0};
+        if (key0 + 4 <= Sk) {
+          m = *reinterpret_cast<const MaskVec*>(mrow + key0);
+        } else if (key0 < Sk) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) m[e] = mrow[min(key0 + e, Sk - 1)];
+        }
+        mreg[kt * 4 + i] = m;
+      }
+    }
+  };
+  // Sub-tile kt's scores with the mask: s = valid ? s * scale_log2 + mask * log2(e) : -inf (the scores live in the exp2
+  // domain; -inf in the mask blocks the key). Key padding here is one byte per lane and tile (key t * 64 + lane, loaded
+  // with the mask runs) and a ballot, not a byte load per score: with those 32 loads in flight beside the mask runs
+  // the D = 128 form does not fit the registers of two workgroups per CU.
+  signed char kpad = 1;
+  unsigned long long kbits = 0;
+  auto add_mask = [&](f32x16& s, int t, int kt) {
+    if (kt == 0) kbits = __ballot(kpad != 0) >> (4 * hf);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kk = kt * 32 + (r & 3) + 8 * (r >> 2);
+      const int key = t * ATT_KV + kk + 4 * hf;
+      const auto m = mreg[kt * 4 + (r >> 2)][r & 3];
+      float mf;
+      if constexpr (MK == ATT_MASK_F32) mf = m;
+      else mf = __uint_as_float((unsigned)(u16)m << 16);
+      const float v = fmaf(mf, 1.4426950408889634f, s[r] * scale_log2);
+      bool valid = key < Sk && ((kbits >> kk) & 1);
+      if (causal) valid = valid && key <= q_row;
+      s[r] = valid ? v : -INFINITY;
+    }
+  };
+
   if (tiles_end > 0) load_tile(0);
   for (int t = 0; t < tiles_end; ++t) {
     __syncthreads();
     store_tile();
     __syncthreads();
     if (t + 1 < tiles_end) load_tile(t + 1);
+    if constexpr (MK != ATT_MASK_NONE) {
+      load_mask(t, 0);
+      load_mask(t, 1);
+      if (key_mask) kpad = key_mask[(long long)b * Sk + min(t * ATT_KV + lane, Sk - 1)];
+    }
 
     // ---- S^T = K Q^T for two 32-key sub-tiles
     f32x16 s[2];
@@ -139,6 +214,7 @@ __global__ __launch_bounds__(256, (DP >= 160 ? 1 : 2)) void flash_fwd_kernel(
         s16x8 a = *reinterpret_cast<const s16x8*>(&Ks[(kt * 32 + l32) * LDW + ks * 16 + 8 * hf]);
         s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), qf[ks], s[kt], 0, 0, 0);
       }
+      if constexpr (MK != ATT_MASK_NONE) add_mask(s[kt], t, kt);
     }
     // ---- masks + online softmax (lane = one query, 32 of the tile's 64 keys)
     float tmax = -INFINITY;
@@ -147,6 +223,10 @@ __global__ __launch_bounds__(256, (DP >= 160 ? 1 : 2)) void flash_fwd_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int key = t * ATT_KV + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+        if constexpr (MK != ATT_MASK_NONE) {   // add_mask has scaled and masked the scores
+          tmax = fmaxf(tmax, s[kt][r]);
+          continue;
+        }
         float v = s[kt][r] * scale_log2;
         bool valid = key < Sk;
         if (key_mask) valid = valid && key_mask[(long long)b * Sk + min(key, Sk - 1)] != 0;
@@ -1009,19 +1089,21 @@ static void launch_attn(Kern kern, dim3 grid, int block, const AttnArgs& a, int 
 
 // The generic kernel for the next head dim >= D it is built for (null: D > 160), and its launch
 using FlashKernel = decltype(&flash_fwd_kernel<32>);
-template <bool BIAS>
+template <bool BIAS, int MK = ATT_MASK_NONE>
 static FlashKernel flash_kernel(int D) {
-  if (D <= 32) return flash_fwd_kernel<32, BIAS>;
-  if (D <= 64) return flash_fwd_kernel<64, BIAS>;
-  if (D <= 96) return flash_fwd_kernel<96, BIAS>;
-  if (D <= 128) return flash_fwd_kernel<128, BIAS>;
-  if (D <= 160) return flash_fwd_kernel<160, BIAS>;
+  if (D <= 32) return flash_fwd_kernel<32, BIAS, MK>;
+  if (D <= 64) return flash_fwd_kernel<64, BIAS, MK>;
+  if (D <= 96) return flash_fwd_kernel<96, BIAS, MK>;
+  if (D <= 128) return flash_fwd_kernel<128, BIAS, MK>;
+  if (D <= 160) return flash_fwd_kernel<160, BIAS, MK>;
   return nullptr;
 }
-static void launch_flash(FlashKernel kern, dim3 grid, const AttnArgs& a, int nqb, AttnBias ab) {
+static const AttnMask kNoMask{nullptr, 0, 0, 0};
+static void launch_flash(FlashKernel kern, dim3 grid, const AttnArgs& a, int nqb, AttnBias ab,
+                         AttnMask am = kNoMask) {
   kern<<<grid, 256, 0, a.stream>>>((const u16*)a.q, (const u16*)a.k, (const u16*)a.v, (u16*)a.o, a.B, a.H, a.Sq, a.Sk,
                                    a.D, a.qsb, a.qss, a.qsh, a.ksb, a.kss, a.ksh, a.vsb, a.vss, a.vsh, a.osb, a.oss,
-                                   a.osh, a.sl2(), (const signed char*)a.key_mask, a.causal, nqb, a.lse, ab);
+                                   a.osh, a.sl2(), (const signed char*)a.key_mask, a.causal, nqb, a.lse, ab, am);
 }
 
 // The short-KV kernel for Sk keys (32-key tiles) and qi 128-query blocks per workgroup, with or without s_setprio
@@ -1209,6 +1291,32 @@ CGS_EXPORT int cgs_flash_attn_fwd_bias(const void* q, const void* k, const void*
   dim3 grid;
   if (!a.grid(ATT_QB, &nqb, &grid)) return (int)hipErrorInvalidValue;
   launch_flash(flash_kernel<true>(D), grid, a, nqb, AttnBias{bias, mask, hscale, nW});
+  return (int)hipGetLastError();
+}
+
+// Generic flash kernel with an additive score mask (AttnMask) of kind ATT_MASK_F32 / ATT_MASK_BF16: msb / msh /
+// msq are its batch / head / query strides in elements (0 broadcasts), the key stride is 1. Composes with key_mask
+// and causal. D <= 160, D % 8 == 0; the mask pointer and every stride a multiple of 4 elements (see AttnMask).
+// Always the generic kernel: the process-wide variant is neither read nor changed.
+CGS_EXPORT int cgs_flash_attn_fwd_mask(const void* q, const void* k, const void* v, void* o, int B, int H, int Sq,
+                                       int Sk, int D, long long qsb, long long qss, long long qsh, long long ksb,
+                                       long long kss, long long ksh, long long vsb, long long vss, long long vsh,
+                                       long long osb, long long oss, long long osh, float scale, const void* mask,
+                                       int kind, long long msb, long long msh, long long msq, const void* key_mask,
+                                       int causal, hipStream_t stream) {
+  if (D % 8 || D > 160 || D <= 0 || !mask || (kind != ATT_MASK_F32 && kind != ATT_MASK_BF16) || B <= 0 || H <= 0 ||
+      Sq <= 0 || Sk <= 0 || msb < 0 || msh < 0 || msq < 0)
+    return (int)hipErrorInvalidValue;
+  const uintptr_t run = kind == ATT_MASK_F32 ? 16 : 8;   // bytes of one 4-key run
+  if (((msb | msh | msq) & 3) || (reinterpret_cast<uintptr_t>(mask) & (run - 1))) return (int)hipErrorInvalidValue;
+  const AttnArgs a{q, k, v, o, B, H, Sq, Sk, D, qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, scale,
+                   key_mask, causal, nullptr, stream};
+  int nqb;
+  dim3 grid;
+  if (!a.grid(ATT_QB, &nqb, &grid)) return (int)hipErrorInvalidValue;
+  const FlashKernel kern = kind == ATT_MASK_F32 ? flash_kernel<false, ATT_MASK_F32>(D)
+                                                : flash_kernel<false, ATT_MASK_BF16>(D);
+  launch_flash(kern, grid, a, nqb, AttnBias{nullptr, nullptr, nullptr, 1}, AttnMask{mask, msb, msh, msq});
   return (int)hipGetLastError();
 }
 

@@ -389,13 +389,69 @@ def _attn_operands(q, k, v, o, heads):
             o.stride(0), o.stride(1), D)
 
 
+_MASK_KIND = {torch.float32: 1, torch.bfloat16: 2}      # ATT_MASK_F32 / ATT_MASK_BF16 of attention.hip
+
+
+def attention_mask_layout(shape, strides, dtype, B, H, Sq, Sk, aligned=True):
+    """How the flash kernel is given a mask of ``shape`` / ``strides`` (elements) / ``dtype`` for scores [B, H, Sq, Sk]:
+    ``(shape4, strides4, kernel dtype, copy)``. Pure: no tensor is touched.
+
+    Accepted shapes, as ``attention_reference`` broadcasts them: [Sq, Sk] -> [1, 1, Sq, Sk], [B|1, Sq, Sk] -> [B|1, 1,
+    Sq, Sk], [B|1, H|1, Sq, Sk]; the query dimension may be 1 as well. Anything else is a ValueError. bool becomes bf16
+    (0 / -inf), fp16 becomes fp32, bf16 and fp32 stay. A size-1 dimension gets stride 0: broadcasting is by stride, never
+    by expanding the mask in memory. The kernel reads a row in 4-element vectors, so the key stride must be 1 and the
+    base (``aligned``: a multiple of 16 bytes) and the other strides multiples of 4 elements; a mask that is converted
+    or does not meet this (Sk = 77 rows, a column slice of a wider tensor) is copied once at its own shape
+    (``copy``), rows padded to a multiple of 8 keys, and the strides returned are those of the copy."""
+    shape, strides = tuple(int(x) for x in shape), tuple(int(x) for x in strides)
+    if len(shape) == 2:
+        shape, strides = (1, 1) + shape, (0, 0) + strides
+    elif len(shape) == 3:
+        shape, strides = (shape[0], 1) + shape[1:], (strides[0], 0) + strides[1:]
+    ok = len(shape) == 4 and all(n in (full, 1) for n, full in zip(shape[:3], (B, H, Sq))) and \
+        (shape[3] == Sk or shape[3] == 1)
+    if not ok or dtype not in (torch.bool, torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"attention mask of shape {shape} / {dtype} does not broadcast to {(B, H, Sq, Sk)}")
+    kdtype = {torch.bool: torch.bfloat16, torch.float16: torch.float32}.get(dtype, dtype)
+    lead = tuple(0 if n == 1 else st for n, st in zip(shape[:3], strides[:3]))
+    copy = (kdtype != dtype or shape[3] != Sk or (Sk > 1 and strides[3] != 1) or not aligned
+            or any(st % 4 or st < 0 for st in lead))
+    if copy:
+        row = (Sk + 7) // 8 * 8
+        dense = (shape[1] * shape[2] * row, shape[2] * row, row)
+        lead = tuple(0 if n == 1 else st for n, st in zip(shape[:3], dense))
+    return shape[:3] + (Sk,), lead + (1,), kdtype, copy
+
+
+def _attn_mask_operand(mask, B, H, Sq, Sk):
+    """``(tensor to keep alive, kind, batch / head / query strides)`` of cgs_flash_attn_fwd_mask. Stream-ordered device
+    work only (capturable): at most one copy of the mask at its own shape, see attention_mask_layout."""
+    shape4, strides4, kdtype, copy = attention_mask_layout(mask.shape, mask.stride(), mask.dtype, B, H, Sq, Sk,
+                                                           mask.data_ptr() % 16 == 0)
+    if copy:
+        m4 = mask.unsqueeze(1) if mask.dim() == 3 else mask.reshape((1,) * (4 - mask.dim()) + tuple(mask.shape))
+        buf = torch.empty(shape4[:3] + ((Sk + 7) // 8 * 8,), device=mask.device, dtype=kdtype)
+        dst = buf[..., :Sk]
+        if mask.dtype == torch.bool:
+            dst.fill_(float("-inf")).masked_fill_(m4, 0.0)
+        else:
+            dst.copy_(m4)
+        mask = buf
+    return mask, _MASK_KIND[kdtype], strides4[:3]
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
               mask: torch.Tensor | None = None, causal: bool = False,
               key_padding: torch.Tensor | None = None) -> torch.Tensor:
     """softmax(q k^T / sqrt(d)) v over ``heads`` heads. q [B,Sq,H*D], k/v [B,Sk,H*D] -> [B,Sq,H*D].
 
     Softmax is accumulated in fp32 (reference upcast semantics, attention.py:104-107).
-    ``mask``: additive float mask broadcastable to [B,H,Sq,Sk] (rare: torch path);
+    ``mask``: additive float mask (-inf blocks a key) or bool mask (True = attend) of shape [Sq,Sk], [B,Sq,Sk] or
+    [B|1,H|1,Sq,Sk]. bf16 q/k/v on the device with a head dim of the flash kernel: the generic flash kernel adds it to
+    the scores in its softmax loop, read through broadcast strides (attention_mask_layout) -- no [B,H,Sq,Sk] score
+    tensor, no expanded mask, composes with ``causal`` and ``key_padding``. A query row whose keys are all blocked
+    comes out as zeros there (the kernel's convention for key padding); the torch path (CPU, other dtypes or head
+    dims) gives NaN for such a row, as torch.softmax does.
     ``causal``: CLIP causal mask; ``key_padding``: bool [B,Sk] True = attend.
     """
     B, Sq, HD = q.shape
@@ -412,6 +468,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
         if o is not None:
             count("attention", "hip")
             return o
+    if (be == "hip" and mask is not None and D in _FLASH_HEAD_DIMS and q.dtype == torch.bfloat16
+            and k.dtype == q.dtype and v.dtype == q.dtype and q.stride(-1) == 1 and k.stride(-1) == 1
+            and v.stride(-1) == 1 and Sk > 0 and mask.device == q.device
+            and _native.has_kernel("cgs_flash_attn_fwd_mask")):
+        m, kind, (msb, msh, msq) = _attn_mask_operand(mask, B, heads, Sq, Sk)
+        kp = None if key_padding is None else key_padding.to(torch.int8).contiguous()
+        o = torch.empty((B, Sq, HD), device=q.device, dtype=q.dtype)
+        _check(_lib().cgs_flash_attn_fwd_mask(*_attn_operands(q, k, v, o, heads), 1.0 / math.sqrt(D), m.data_ptr(),
+                                              kind, msb, msh, msq, _ptr(kp), 1 if causal else 0, _stream()),
+               "cgs_flash_attn_fwd_mask")
+        count("attention", "hip")
+        return o
     wide_ok = D == 512 and not causal and key_padding is None
     if (be == "hip" and mask is None and (D in _FLASH_HEAD_DIMS or wide_ok) and q.dtype == torch.bfloat16
             and q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1):
