@@ -31,6 +31,14 @@ inline int num_cus() {
   return n;
 }
 
+// hipFuncAttributeMaxDynamicSharedMemorySize = bytes on Kern, once per process (before Kern's first launch)
+template <auto Kern>
+inline void max_dynamic_lds_once(int bytes) {
+  static const hipError_t set =
+      hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  (void)set;
+}
+
 __device__ __forceinline__ float bf2f(u16 v) {
   return __uint_as_float(((uint32_t)v) << 16);
 }

@@ -52,9 +52,14 @@ struct ConvArgs {
   float act_param;     //   (variants 3 / 4 / 8) through cgs_conv2d_nhwc_act; act_param = the leaky_relu slope
 };
 
-// The mc::tile epilogue of a conv: bias / residual from the flags, the activation through MC_EPI_GELU + code.
+// The epilogue of a conv: bias / residual from the flags.
+__device__ __forceinline__ mc::Epi conv_epi(const ConvArgs& a) {
+  return mc::Epi{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+}
+// The mc::tile epilogue of a conv with an activation (the ACT instantiations only): conv_epi plus the activation
+// through MC_EPI_GELU + code.
 __device__ __forceinline__ mc::Epi conv_tile_epi(const ConvArgs& a) {
-  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  mc::Epi e = conv_epi(a);
   if (a.act) {
     e.flags |= MC_EPI_GELU;
     e.act = a.act;
@@ -68,6 +73,21 @@ static void conv_magic(ConvArgs& a) {
   const unsigned cq = (unsigned)(a.Cin / 64);
   a.cq_magic = cq <= 1 ? 0u : (unsigned)(((1ull << 32) + cq - 1) / cq);
   a.kw_m16 = (65536 + a.kw - 1) / a.kw;
+}
+
+// Host: the BM x BN output tiles of a. Sets a.tiles_n and returns their number: the grid of the kernels that run
+// one tile per workgroup, and what the persistent ones cap at the CU count.
+static long long conv_tiles(ConvArgs& a, int BM, int BN) {
+  const int M = a.N * a.Ho * a.Wo;
+  a.tiles_n = (a.Cout + BN - 1) / BN;
+  return (long long)((M + BM - 1) / BM) * a.tiles_n;
+}
+
+// Host: launch Kern on a with lds bytes of dynamic LDS (raised to that before Kern's first launch).
+template <auto Kern>
+static void conv_run(const ConvArgs& a, long long grid, int threads, int lds, hipStream_t stream) {
+  max_dynamic_lds_once<Kern>(lds);
+  Kern<<<(unsigned)grid, threads, lds, stream>>>(a);
 }
 
 template <int BN>
@@ -260,26 +280,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
   grouped_tile(logical, gridDim.x / a.tiles_n, a.tiles_n, a.group_m, tm, tn);
   ConvGatherA al;
   al.a = &a;
-  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  mc::Epi e = conv_epi(a);
   if constexpr (ACT) e = conv_tile_epi(a);
   mc::tile<BN, NW>(al, a.w, K, M, a.Cout, K, tm * mc::BM, tn * BN, e, smem);
 }
 
 template <int BN, int NW>
 static void conv_v3_go(ConvArgs& a, hipStream_t stream) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v3_kernel<BN, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              mc::Cfg<BN, NW>::LDS);
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v3_kernel<BN, NW, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, mc::Cfg<BN, NW>::LDS);
-    attr = true;
-  }
-  const int M = a.N * a.Ho * a.Wo;
-  a.tiles_n = (a.Cout + BN - 1) / BN;
-  const long long nwg = (long long)((M + mc::BM - 1) / mc::BM) * a.tiles_n;
-  if (a.act) conv_nhwc_v3_kernel<BN, NW, true><<<(unsigned)nwg, 64 * NW, mc::Cfg<BN, NW>::LDS, stream>>>(a);
-  else conv_nhwc_v3_kernel<BN, NW><<<(unsigned)nwg, 64 * NW, mc::Cfg<BN, NW>::LDS, stream>>>(a);
+  constexpr int lds = mc::Cfg<BN, NW>::LDS;
+  const long long nwg = conv_tiles(a, mc::BM, BN);
+  if (!a.act) conv_run<conv_nhwc_v3_kernel<BN, NW>>(a, nwg, 64 * NW, lds, stream);
+  else conv_run<conv_nhwc_v3_kernel<BN, NW, true>>(a, nwg, 64 * NW, lds, stream);
 }
 
 // v8: the v3 main loop on 128 x 128 tiles (two workgroups per CU) for short grids -- the level-2
@@ -294,26 +305,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   grouped_tile(logical, gridDim.x / a.tiles_n, a.tiles_n, a.group_m, tm, tn);
   ConvGatherA al;
   al.a = &a;
-  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  mc::Epi e = conv_epi(a);
   if constexpr (ACT) e = conv_tile_epi(a);
   mc::tile<128, 4, ConvGatherA, 128>(al, a.w, K, M, a.Cout, K, tm * 128, tn * 128, e, smem);
 }
 
 static void conv_v8_go(ConvArgs& a, hipStream_t stream) {
-  using Cf = mc::Cfg<128, 4, 128>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              Cf::LDS);
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              Cf::LDS);
-    attr = true;
-  }
-  const int M = a.N * a.Ho * a.Wo;
-  a.tiles_n = (a.Cout + 127) / 128;
-  const long long nwg = (long long)((M + 127) / 128) * a.tiles_n;
-  if (a.act) conv_nhwc_v8_kernel<true><<<(unsigned)nwg, 256, Cf::LDS, stream>>>(a);
-  else conv_nhwc_v8_kernel<false><<<(unsigned)nwg, 256, Cf::LDS, stream>>>(a);
+  constexpr int lds = mc::Cfg<128, 4, 128>::LDS;
+  const long long nwg = conv_tiles(a, 128, 128);
+  if (!a.act) conv_run<conv_nhwc_v8_kernel<false>>(a, nwg, 256, lds, stream);
+  else conv_run<conv_nhwc_v8_kernel<true>>(a, nwg, 256, lds, stream);
 }
 
 // v5: ping-pong schedule (mfma_pp.h), 256 x 256 x 64 tiles; Cin % 64 == 0 (one tap per K-tile).
@@ -633,17 +634,15 @@ static bool conv_wide(const ConvArgs& a) {
   const long long px = (long long)a.N * a.H * a.W;
   return px * a.C1 * 2 >= (1ll << 31) || (a.in2 && px * (a.Cin - a.C1) * 2 >= (1ll << 31));
 }
-// ConvGatherKD applies (sets a.img_rsrc): every input < 2 GiB, or each image < 2 GiB with 256-row output
-// tiles that never straddle two images
-static bool conv_kd(ConvArgs& a) {
-  a.img_rsrc = 0;
-  if ((a.flags & CONV_UP2X) && (a.in2 || a.kh * a.kw > 32 || a.H >= 32768 || a.W >= 32768)) return false;
-  if (!conv_wide(a)) return true;
+// ConvGatherKD / KU apply: 1 when every input is < 2 GiB, 2 (the kernel then needs a.img_rsrc = 1) when each image
+// is < 2 GiB with 256-row output tiles that never straddle two images, 0 otherwise
+static int conv_kd(const ConvArgs& a) {
+  if ((a.flags & CONV_UP2X) && (a.in2 || a.kh * a.kw > 32 || a.H >= 32768 || a.W >= 32768)) return 0;
+  if (!conv_wide(a)) return 1;
   const long long px = (long long)a.H * a.W;
   const bool img_ok = ((long long)a.Ho * a.Wo) % 256 == 0 && px * a.C1 * 2 < (1ll << 31) &&
                       (!a.in2 || px * (a.Cin - a.C1) * 2 < (1ll << 31));
-  a.img_rsrc = img_ok ? 1 : 0;
-  return img_ok;
+  return img_ok ? 2 : 0;
 }
 
 template <bool KD>   // KD: ConvGatherKD (buffer_load ... lds); else ConvGatherK with 64-bit offsets
@@ -657,7 +656,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   typename std::conditional<KD, ConvGatherKD, ConvGatherK<true>>::type al;
   al.a = &a;
   if constexpr (KD) al.init();
-  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  mc::Epi e = conv_epi(a);
   pp::tile(al, a.w, K, M, a.Cout, K, tm * pp::BM, tn * pp::BN, e, smem);
 }
 
@@ -672,7 +671,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   typename std::conditional<KU, ConvGatherKU, ConvGatherA8>::type al;
   al.a = &a;
   if constexpr (KU) al.init();
-  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  mc::Epi e = conv_epi(a);
   pp::tile(al, a.w, K, M, a.Cout, K, tm * pp::BM, tn * pp::BN, e, smem);
 }
 
@@ -685,40 +684,50 @@ static int conv_loader_env() {
 static int g_conv_v6_ld = conv_loader_env();
 CGS_EXPORT void cgs_conv_v6_set_loader(int ld) { g_conv_v6_ld = ld; }
 
+// v5 keeps its own reading of the override: 0 leaves KD on the fast path, 1 leaves KU on the upsample path.
 static void conv_v5_go(ConvArgs& a, hipStream_t stream) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v5_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              pp::LDS);
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v5_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              pp::LDS);
-    attr = true;
+  const long long nwg = conv_tiles(a, pp::BM, pp::BN);
+  const int kd = conv_kd(a);
+  a.img_rsrc = kd == 2;
+  if (!conv_fast_ok(a)) {
+    const bool ku = (a.flags & CONV_UP2X) && g_conv_v6_ld != 0 && kd;
+    if (ku) conv_magic(a);
+    if (!ku) conv_run<conv_nhwc_v5_kernel<false>>(a, nwg, pp::THREADS, pp::LDS, stream);
+    else conv_run<conv_nhwc_v5_kernel<true>>(a, nwg, pp::THREADS, pp::LDS, stream);
+    return;
   }
-  const int M = a.N * a.Ho * a.Wo;
-  a.tiles_n = (a.Cout + pp::BN - 1) / pp::BN;
-  const long long nwg = (long long)((M + pp::BM - 1) / pp::BM) * a.tiles_n;
-  if (conv_fast_ok(a)) {
-    static bool attr_k = false;
-    if (!attr_k) {
-      (void)hipFuncSetAttribute((const void*)conv_nhwc_v5k_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                pp::LDS);
-      (void)hipFuncSetAttribute((const void*)conv_nhwc_v5k_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                pp::LDS);
-      attr_k = true;
-    }
-    conv_magic(a);
-    if (g_conv_v6_ld != 1 && conv_kd(a)) conv_nhwc_v5k_kernel<true><<<(unsigned)nwg, pp::THREADS, pp::LDS, stream>>>(a);
-    else conv_nhwc_v5k_kernel<false><<<(unsigned)nwg, pp::THREADS, pp::LDS, stream>>>(a);
-  } else if ((a.flags & CONV_UP2X) && g_conv_v6_ld != 0 && conv_kd(a)) {
-    conv_magic(a);
-    conv_nhwc_v5_kernel<true><<<(unsigned)nwg, pp::THREADS, pp::LDS, stream>>>(a);
-  } else {
-    conv_nhwc_v5_kernel<false><<<(unsigned)nwg, pp::THREADS, pp::LDS, stream>>>(a);
-  }
+  conv_magic(a);
+  if (g_conv_v6_ld != 1 && kd) conv_run<conv_nhwc_v5k_kernel<true>>(a, nwg, pp::THREADS, pp::LDS, stream);
+  else conv_run<conv_nhwc_v5k_kernel<false>>(a, nwg, pp::THREADS, pp::LDS, stream);
+}
+
+// The gather of the pq kernels (v6, v6w4) for a, LD as at conv_nhwc_v6_kernel: KD / KU where they apply, else K on
+// the fast path and A8 off it; an override below that choice replaces it (KU falls to A8). Sets what the chosen
+// gather reads: a.img_rsrc and the conv_magic constants.
+static int conv_pq_loader(ConvArgs& a) {
+  const int kd = conv_kd(a);
+  int ld = conv_fast_ok(a) ? (kd ? 2 : 1) : ((a.flags & CONV_UP2X) && kd ? 3 : 0);
+  if (g_conv_v6_ld >= 0 && g_conv_v6_ld < ld) ld = ld == 3 ? 0 : g_conv_v6_ld;
+  a.img_rsrc = ld >= 2 && kd == 2;
+  if (ld) conv_magic(a);
+  return ld;
+}
+// f(std::integral_constant<int, ld>{}) for ld = 0..3
+template <typename F>
+static void with_loader(int ld, F f) {
+  if (ld == 3) f(std::integral_constant<int, 3>{});
+  else if (ld == 2) f(std::integral_constant<int, 2>{});
+  else if (ld == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
 }
 
 // LD: 0 ConvGatherA8 (generic: UP2X, big filters), 1 ConvGatherK (64-bit offsets: an input >= 2 GiB),
-// 2 ConvGatherKD (buffer_load ... lds, the default where it applies)
+// 2 ConvGatherKD (buffer_load ... lds, the default where it applies), 3 ConvGatherKU (its upsample-aware form)
+template <int LD>
+using ConvLoaderFor = typename std::conditional<
+    LD == 3, ConvGatherKU,
+    typename std::conditional<LD == 2, ConvGatherKD,
+                              typename std::conditional<LD == 1, ConvGatherK<true>, ConvGatherA8>::type>::type>::type;
 // NJ: 16-column MFMA tiles per wave group -- 5 (256 x 160 tiles) or 4 (256 x 128: Cout = 128 / 256 / 384 ...,
 // variant 18)
 template <int LD, int DS = 0, bool GNS = false, int NJ = 5, int PFE = CGS_CONV_PFE>
@@ -726,13 +735,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int M = a.N * a.Ho * a.Wo;
   const int K = a.kh * a.kw * a.Cin;
-  typename std::conditional<
-      LD == 3, ConvGatherKU,
-      typename std::conditional<LD == 2, ConvGatherKD,
-                                typename std::conditional<LD == 1, ConvGatherK<true>, ConvGatherA8>::type>::type>::type al;
+  ConvLoaderFor<LD> al;
   al.a = &a;
   if constexpr (LD >= 2) al.init();
-  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  mc::Epi e = conv_epi(a);
   e.gnp = a.gnp;
   e.hw = a.Ho * a.Wo;
   pq::run<decltype(al), false, DS, GNS, false, false, false, PFE, NJ>(al, a.w, K, M, a.Cout, K, e, smem,
@@ -747,13 +753,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int M = a.N * a.Ho * a.Wo;
   const int K = a.kh * a.kw * a.Cin;
-  typename std::conditional<
-      LD == 3, ConvGatherKU,
-      typename std::conditional<LD == 2, ConvGatherKD,
-                                typename std::conditional<LD == 1, ConvGatherK<true>, ConvGatherA8>::type>::type>::type al;
+  ConvLoaderFor<LD> al;
   al.a = &a;
   if constexpr (LD >= 2) al.init();
-  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  mc::Epi e = conv_epi(a);
   using Gm = pq::Geo<5, 2, 4>;
   pq::run<decltype(al), false, 51, false, false, false, false, 0, 5, 2, 4>(al, a.w, K, M, a.Cout, K, e, smem,
                                                                           (M + Gm::BM - 1) / Gm::BM, a.tiles_n,
@@ -764,55 +767,24 @@ int v6_conv_ds();   // gemm.hip: v6 DMA placement for convs (CGS_V6_CONV_DS / cg
 
 template <int LD, int DS, bool GNS = false, int NJ = 5, int PFE = CGS_CONV_PFE>
 static void conv_v6_launch(ConvArgs& a, int grid, hipStream_t stream) {
-  constexpr int lds = pq::Geo<NJ>::LDS;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v6_kernel<LD, DS, GNS, NJ, PFE>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
-  conv_nhwc_v6_kernel<LD, DS, GNS, NJ, PFE><<<grid, pq::THREADS, lds, stream>>>(a);
+  conv_run<conv_nhwc_v6_kernel<LD, DS, GNS, NJ, PFE>>(a, grid, pq::THREADS, pq::Geo<NJ>::LDS, stream);
 }
-
-
 
 static void conv_v6w4_go(ConvArgs& a, hipStream_t stream) {
   using Gm = pq::Geo<5, 2, 4>;
-  const int M = a.N * a.Ho * a.Wo;
-  a.tiles_n = (a.Cout + Gm::BN - 1) / Gm::BN;
-  const long long T = (long long)((M + Gm::BM - 1) / Gm::BM) * a.tiles_n;
+  const long long T = conv_tiles(a, Gm::BM, Gm::BN);
   const int grid = (int)(T < 2 * num_cus() ? T : 2 * num_cus());
-  int ld = conv_fast_ok(a) ? (conv_kd(a) ? 2 : 1) : ((a.flags & CONV_UP2X) && conv_kd(a) ? 3 : 0);
-  if (g_conv_v6_ld >= 0 && g_conv_v6_ld < ld) ld = ld == 3 ? 0 : g_conv_v6_ld;
-  if (ld) conv_magic(a);
-  auto go = [&](auto lc) {
-    constexpr int L = decltype(lc)::value;
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)conv_nhwc_v6w4_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                Gm::LDS);
-      attr = true;
-    }
-    conv_nhwc_v6w4_kernel<L><<<grid, 256, Gm::LDS, stream>>>(a);
-  };
-  if (ld == 3) go(std::integral_constant<int, 3>{});
-  else if (ld == 2) go(std::integral_constant<int, 2>{});
-  else if (ld == 1) go(std::integral_constant<int, 1>{});
-  else go(std::integral_constant<int, 0>{});
+  with_loader(conv_pq_loader(a), [&](auto lc) {
+    conv_run<conv_nhwc_v6w4_kernel<decltype(lc)::value>>(a, grid, 256, Gm::LDS, stream);
+  });
 }
 
 static void conv_v6_go(ConvArgs& a, hipStream_t stream, bool n128 = false) {
-  const int M = a.N * a.Ho * a.Wo;
   if (a.gnp) n128 = false;   // the GroupNorm-statistics epilogue: 160-wide tiles only
-  const int bn = n128 ? pq::Geo<4>::BN : pq::BN;
-  a.tiles_n = (a.Cout + bn - 1) / bn;
-  const long long T = (long long)((M + pq::BM - 1) / pq::BM) * a.tiles_n;
+  const long long T = conv_tiles(a, pq::BM, n128 ? pq::Geo<4>::BN : pq::BN);
   const int grid = (int)(T < num_cus() ? T : num_cus());
   const int ds = v6_conv_ds();
-  int ld = conv_fast_ok(a) ? (conv_kd(a) ? 2 : 1) : ((a.flags & CONV_UP2X) && conv_kd(a) ? 3 : 0);
-  if (g_conv_v6_ld >= 0 && g_conv_v6_ld < ld) ld = ld == 3 ? 0 : g_conv_v6_ld;
-  if (ld) conv_magic(a);
-  auto go = [&](auto lc) {
+  with_loader(conv_pq_loader(a), [&](auto lc) {
     constexpr int L = decltype(lc)::value;
     if (a.gnp) {   // GroupNorm statistics epilogue (split-DMA main loop only)
       conv_v6_launch<L, 51, true>(a, grid, stream);
@@ -831,11 +803,7 @@ static void conv_v6_go(ConvArgs& a, hipStream_t stream, bool n128 = false) {
       case 1: conv_v6_launch<L, 1>(a, grid, stream); break;
       default: conv_v6_launch<L, 51>(a, grid, stream);
     }
-  };
-  if (ld == 3) go(std::integral_constant<int, 3>{});
-  else if (ld == 2) go(std::integral_constant<int, 2>{});
-  else if (ld == 1) go(std::integral_constant<int, 1>{});
-  else go(std::integral_constant<int, 0>{});
+  });
 }
 
 // v7: the persistent 256 x 256 ping-pong with cross-tile prefetch and register epilogue (mfma_ppk.h)
@@ -850,25 +818,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                             typename std::conditional<LOADER == 1, ConvGatherKB, ConvGatherA8>::type>::type al;
   al.a = &a;
   if constexpr (LOADER >= 1) al.init();
-  mc::Epi e{a.out, a.bias, a.res, a.Cout, a.Cout, a.flags & (EPI_BIAS | EPI_RESIDUAL), 1.0f};
+  mc::Epi e = conv_epi(a);
   ppk::run<false>(al, a.w, K, M, a.Cout, K, e, smem, (M + ppk::BM - 1) / ppk::BM, a.tiles_n, a.group_m, a.sp);
 }
 
 static void conv_v7_go(ConvArgs& a, hipStream_t stream, void* ws = nullptr, long long ws_bytes = 0) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v7_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ppk::LDS);
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v7_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ppk::LDS);
-    (void)hipFuncSetAttribute((const void*)conv_nhwc_v7_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ppk::LDS);
-    attr = true;
-  }
-  const int M = a.N * a.Ho * a.Wo;
   const int K = a.kh * a.kw * a.Cin;
-  a.tiles_n = (a.Cout + ppk::BN - 1) / ppk::BN;
-  const long long T = (long long)((M + ppk::BM - 1) / ppk::BM) * a.tiles_n;
+  const long long T = conv_tiles(a, ppk::BM, ppk::BN);
   a.sp = ppk::Split{0, 1, nullptr, nullptr, 0};
   long long U = T;
   if (ws && ws_bytes >= ppk::split_ws_bytes(T, K / ppk::BK, num_cus())) {
@@ -883,14 +839,13 @@ static void conv_v7_go(ConvArgs& a, hipStream_t stream, void* ws = nullptr, long
     }
   }
   const int grid = (int)(U < num_cus() ? U : num_cus());
-  if (conv_fast_ok(a) && !conv_wide(a)) {
-    conv_magic(a);
-    a.img_rsrc = 0;
-    if (g_conv_v6_ld == 1) conv_nhwc_v7_kernel<1><<<grid, ppk::THREADS, ppk::LDS, stream>>>(a);
-    else conv_nhwc_v7_kernel<2><<<grid, ppk::THREADS, ppk::LDS, stream>>>(a);
-  } else {
-    conv_nhwc_v7_kernel<0><<<grid, ppk::THREADS, ppk::LDS, stream>>>(a);
+  if (!conv_fast_ok(a) || conv_wide(a)) {
+    conv_run<conv_nhwc_v7_kernel<0>>(a, grid, ppk::THREADS, ppk::LDS, stream);
+    return;
   }
+  conv_magic(a);   // v7's own buffer loaders: the override picks KB (1) over KL, nothing else
+  if (g_conv_v6_ld == 1) conv_run<conv_nhwc_v7_kernel<1>>(a, grid, ppk::THREADS, ppk::LDS, stream);
+  else conv_run<conv_nhwc_v7_kernel<2>>(a, grid, ppk::THREADS, ppk::LDS, stream);
 }
 
 static int g_conv_group = 8;
@@ -898,41 +853,35 @@ CGS_EXPORT void cgs_conv_set_tile_group(int g) { g_conv_group = g < 1 ? 1 : g; }
 static int g_conv_variant = -1;   // -1 auto (v3/8 waves where legal), 2 = v2 only, 3 = v3/4 waves, 4 = v3/8 waves
 CGS_EXPORT void cgs_conv_set_variant(int v) { g_conv_variant = v; }
 
+// The domain of the variants whose K step is 64 wide (5, 6, 7, 18, 21); any other variant has no rule here.
+static bool conv_variant_ok(const ConvArgs& a, int variant) {
+  if (variant != 5 && variant != 6 && variant != 7 && variant != 18 && variant != 21) return true;
+  if (a.Cin % 64 || (a.in2 && a.C1 % 64)) return false;
+  if (variant == 5) return true;
+  if (a.kh * a.kw * a.Cin < 128 || (uintptr_t)a.bias % 8) return false;
+  if (variant == 7) return (long long)a.Cout * a.kh * a.kw * a.Cin * 2 < (1ll << 32);   // weights under 4 GiB
+  if (variant == 18) return a.Cout % 128 == 0;
+  if (variant == 21) return a.Cout % 80 == 0 && a.gnp == nullptr;
+  return true;
+}
+
 static int conv_v3_launch(ConvArgs& a, int variant, hipStream_t stream, void* ws = nullptr, long long ws_bytes = 0) {
-  a.group_m = g_conv_group;
-  if (variant == 5 && a.Cin % 64 == 0 && (a.in2 == nullptr || a.C1 % 64 == 0)) {
-    conv_v5_go(a, stream);
-    return (int)hipGetLastError();
+  switch (conv_variant_ok(a, variant) ? variant : 4) {
+    case 5: conv_v5_go(a, stream); break;
+    case 6: conv_v6_go(a, stream); break;
+    case 7: conv_v7_go(a, stream, ws, ws_bytes); break;
+    case 18: conv_v6_go(a, stream, true); break;
+    case 21: conv_v6w4_go(a, stream); break;
+    case 8: conv_v8_go(a, stream); break;
+    default: {   // the v3 tile: 4 waves for variant 3, 8 otherwise -- a request outside its variant's domain too
+      const bool w8 = variant != 3;
+      if (mc::pick_bn(a.N * a.Ho * a.Wo, a.Cout) == 256) {
+        if (w8) conv_v3_go<256, 8>(a, stream); else conv_v3_go<256, 4>(a, stream);
+      } else {
+        if (w8) conv_v3_go<128, 8>(a, stream); else conv_v3_go<128, 4>(a, stream);
+      }
+    }
   }
-  if (variant == 7 && a.Cin % 64 == 0 && (a.in2 == nullptr || a.C1 % 64 == 0) && a.kh * a.kw * a.Cin >= 128 &&
-      ((uintptr_t)a.bias % 8) == 0 && (long long)a.Cout * a.kh * a.kw * a.Cin * 2 < (1ll << 32)) {
-    conv_v7_go(a, stream, ws, ws_bytes);
-    return (int)hipGetLastError();
-  }
-  if (variant == 6 && a.Cin % 64 == 0 && (a.in2 == nullptr || a.C1 % 64 == 0) && a.kh * a.kw * a.Cin >= 128 &&
-      ((uintptr_t)a.bias % 8) == 0) {
-    conv_v6_go(a, stream);
-    return (int)hipGetLastError();
-  }
-  if (variant == 21 && a.Cin % 64 == 0 && (a.in2 == nullptr || a.C1 % 64 == 0) && a.kh * a.kw * a.Cin >= 128 &&
-      ((uintptr_t)a.bias % 8) == 0 && a.Cout % 80 == 0 && a.gnp == nullptr) {
-    conv_v6w4_go(a, stream);
-    return (int)hipGetLastError();
-  }
-  if (variant == 18 && a.Cin % 64 == 0 && (a.in2 == nullptr || a.C1 % 64 == 0) && a.kh * a.kw * a.Cin >= 128 &&
-      ((uintptr_t)a.bias % 8) == 0 && a.Cout % 128 == 0) {
-    conv_v6_go(a, stream, true);
-    return (int)hipGetLastError();
-  }
-  if (variant == 8) {
-    conv_v8_go(a, stream);
-    return (int)hipGetLastError();
-  }
-  const int M = a.N * a.Ho * a.Wo;
-  const int BN = mc::pick_bn(M, a.Cout);
-  const bool w8 = variant != 3;
-  if (BN == 256) { if (w8) conv_v3_go<256, 8>(a, stream); else conv_v3_go<256, 4>(a, stream); }
-  else { if (w8) conv_v3_go<128, 8>(a, stream); else conv_v3_go<128, 4>(a, stream); }
   return (int)hipGetLastError();
 }
 
@@ -1156,34 +1105,35 @@ static int conv_launch(ConvArgs& a, hipStream_t stream, int variant = -2, void* 
   // v3 needs Cout % 8 == 0 for the 16-B epilogue stores (SD/SDXL/VAE convs: all but the 3/4-channel
   // heads, which take v2).
   if (variant != 2 && a.Cout % 8 == 0) return conv_v3_launch(a, variant, stream, ws, ws_bytes);
-  a.group_m = g_conv_group;
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute((const void*)conv_nhwc_v2_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        2 * (256 * 64 * 2 + 256 * 64 * 2));
-    hipFuncSetAttribute((const void*)conv_nhwc_v2_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        2 * (256 * 64 * 2 + 128 * 64 * 2));
-    attr = true;
-  }
-  const int M = a.N * a.Ho * a.Wo;
-  const bool wide = a.Cout >= 1024;
-  const int BN = wide ? 256 : 128;
-  a.tiles_n = (a.Cout + BN - 1) / BN;
-  long long nwg = (long long)((M + 255) / 256) * a.tiles_n;
-  size_t lds = 2 * (256 * 64 * 2 + BN * 64 * 2);
-  if (wide) conv_nhwc_v2_kernel<256><<<(unsigned)nwg, 512, lds, stream>>>(a);
-  else conv_nhwc_v2_kernel<128><<<(unsigned)nwg, 512, lds, stream>>>(a);
+  // two stages of a 256 x 64 A tile and a BN x 64 B tile
+  if (a.Cout >= 1024) conv_run<conv_nhwc_v2_kernel<256>>(a, conv_tiles(a, 256, 256), 512, 4 * 64 * (256 + 256), stream);
+  else conv_run<conv_nhwc_v2_kernel<128>>(a, conv_tiles(a, 256, 128), 512, 4 * 64 * (256 + 128), stream);
   return (int)hipGetLastError();
+}
+
+// The operands of one call as the kernels' argument: epilogue flags from bias / res (+ CONV_UP2X of flags), C1 = Cin
+// without a second input, the process-wide tile group; everything a launcher or an entry fills in later is zero.
+static ConvArgs conv_args(const void* x, const void* x2, int C1, const void* w, const void* bias, const void* res,
+                          void* out, int N, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                          int Ho, int Wo, int flags) {
+  return ConvArgs{(const u16*)x, (const u16*)x2, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W,
+                  Cin, x2 ? C1 : Cin, Cout, kh, kw, stride, pad, Ho, Wo,
+                  (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0) | (flags & CONV_UP2X), 0, g_conv_group};
+}
+
+// What every general entry needs: 32-wide K steps inside one tap and one input; Cout <= 16 takes the narrow-output
+// kernel, Cout % 8 == 0 the v3 family, anything else the v2 tile (64-wide K steps).
+static bool conv_shape_ok(const ConvArgs& a) {
+  return !(a.Cin % 32 || (a.in2 && a.C1 % 32) || a.Cout < 1 ||
+           (a.Cout % 8 && a.Cout > 16 && (a.Cin % 64 || (a.in2 && a.C1 % 64))));
 }
 
 // x [N,H,W,Cin] NHWC bf16, w [Cout,kh,kw,Cin], bias [Cout] | null, res [N,Ho,Wo,Cout] | null.
 CGS_EXPORT int cgs_conv2d_nhwc(const void* x, const void* w, const void* bias, const void* res, void* out, int N, int H,
                                int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int Ho, int Wo,
                                hipStream_t stream) {
-  if (Cin % 32 || Cout < 1 || (Cout % 8 && Cout > 16 && Cin % 64)) return (int)hipErrorInvalidValue;
-  ConvArgs a{(const u16*)x, nullptr, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W, Cin, Cin,
-             Cout, kh, kw, stride, pad, Ho, Wo, (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0), 0, 1};
-  return conv_launch(a, stream);
+  ConvArgs a = conv_args(x, nullptr, Cin, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, 0);
+  return conv_shape_ok(a) ? conv_launch(a, stream) : (int)hipErrorInvalidValue;
 }
 
 // Fused variants: flags may carry CONV_UP2X (input read through nearest-2x upsample); x2 != null
@@ -1191,24 +1141,16 @@ CGS_EXPORT int cgs_conv2d_nhwc(const void* x, const void* w, const void* bias, c
 CGS_EXPORT int cgs_conv2d_nhwc_ex(const void* x, const void* x2, int C1, const void* w, const void* bias,
                                   const void* res, void* out, int N, int H, int W, int Cin, int Cout, int kh, int kw,
                                   int stride, int pad, int Ho, int Wo, int flags, hipStream_t stream) {
-  if (Cin % 32 || (x2 && (C1 % 32)) || Cout < 1 || (Cout % 8 && Cout > 16 && (Cin % 64 || (x2 && C1 % 64))))
-    return (int)hipErrorInvalidValue;
-  ConvArgs a{(const u16*)x, (const u16*)x2, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W,
-             Cin, x2 ? C1 : Cin, Cout, kh, kw, stride, pad, Ho, Wo,
-             (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0) | (flags & CONV_UP2X), 0, 1};
-  return conv_launch(a, stream);
+  ConvArgs a = conv_args(x, x2, C1, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, flags);
+  return conv_shape_ok(a) ? conv_launch(a, stream) : (int)hipErrorInvalidValue;
 }
 
 // Per-call kernel choice for the autotuner (variant as in cgs_conv_set_variant; flags as _ex).
 CGS_EXPORT int cgs_conv2d_nhwc_v(const void* x, const void* x2, int C1, const void* w, const void* bias,
                                  const void* res, void* out, int N, int H, int W, int Cin, int Cout, int kh, int kw,
                                  int stride, int pad, int Ho, int Wo, int flags, int variant, hipStream_t stream) {
-  if (Cin % 32 || (x2 && (C1 % 32)) || Cout < 1 || (Cout % 8 && Cout > 16 && (Cin % 64 || (x2 && C1 % 64))))
-    return (int)hipErrorInvalidValue;
-  ConvArgs a{(const u16*)x, (const u16*)x2, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W,
-             Cin, x2 ? C1 : Cin, Cout, kh, kw, stride, pad, Ho, Wo,
-             (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0) | (flags & CONV_UP2X), 0, 1};
-  return conv_launch(a, stream, variant);
+  ConvArgs a = conv_args(x, x2, C1, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, flags);
+  return conv_shape_ok(a) ? conv_launch(a, stream, variant) : (int)hipErrorInvalidValue;
 }
 
 // cgs_conv2d_nhwc_v with an activation of the set (CgsAct, common.h) on acc + bias, before the residual add:
@@ -1218,12 +1160,10 @@ CGS_EXPORT int cgs_conv2d_nhwc_act(const void* x, const void* x2, int C1, const 
                                    const void* res, void* out, int N, int H, int W, int Cin, int Cout, int kh, int kw,
                                    int stride, int pad, int Ho, int Wo, int flags, int variant, int act,
                                    float act_param, hipStream_t stream) {
-  if (Cin % 32 || (x2 && (C1 % 32)) || Cout <= 16 || Cout % 8 || (variant != 3 && variant != 4 && variant != 8) ||
+  ConvArgs a = conv_args(x, x2, C1, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, flags);
+  if (!conv_shape_ok(a) || Cout <= 16 || Cout % 8 || (variant != 3 && variant != 4 && variant != 8) ||
       act < CGS_ACT_NONE || act > CGS_ACT_LEAKY_RELU)
     return (int)hipErrorInvalidValue;
-  ConvArgs a{(const u16*)x, (const u16*)x2, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W,
-             Cin, x2 ? C1 : Cin, Cout, kh, kw, stride, pad, Ho, Wo,
-             (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0) | (flags & CONV_UP2X), 0, 1};
   a.act = act;
   a.act_param = act_param;
   return conv_launch(a, stream, variant);
@@ -1231,18 +1171,14 @@ CGS_EXPORT int cgs_conv2d_nhwc_act(const void* x, const void* x2, int C1, const 
 
 // v6 conv whose epilogue also writes the GroupNorm partial statistics of its output (gnp: [N, Ho*Wo/64,
 // Cout] (mean, M2) float pairs, the cgs_groupnorm_nhwc_part layout with 64 pixels per block), so the
-// following GroupNorm skips its statistics pass. Needs (Ho * Wo) % 256 == 0 and the v6 conditions.
+// following GroupNorm skips its statistics pass. Needs (Ho * Wo) % 256 == 0, Cout % 8 == 0 and the v6 domain.
 CGS_EXPORT int cgs_conv2d_nhwc_gns(const void* x, const void* x2, int C1, const void* w, const void* bias,
                                    const void* res, void* out, int N, int H, int W, int Cin, int Cout, int kh, int kw,
                                    int stride, int pad, int Ho, int Wo, int flags, float* gnp, hipStream_t stream) {
-  if (!gnp || Cin % 64 || (x2 && C1 % 64) || Cout % 8 || kh * kw * Cin < 128 || (Ho * Wo) % 256 ||
-      ((uintptr_t)bias % 8) || ((uintptr_t)gnp % 16))
+  ConvArgs a = conv_args(x, x2, C1, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, flags);
+  if (!gnp || ((uintptr_t)gnp % 16) || (Ho * Wo) % 256 || Cout % 8 || !conv_variant_ok(a, 6))
     return (int)hipErrorInvalidValue;
-  ConvArgs a{(const u16*)x, (const u16*)x2, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W,
-             Cin, x2 ? C1 : Cin, Cout, kh, kw, stride, pad, Ho, Wo,
-             (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0) | (flags & CONV_UP2X), 0, 1};
   a.gnp = gnp;
-  a.group_m = g_conv_group;
   conv_v6_go(a, stream);
   return (int)hipGetLastError();
 }
@@ -1252,10 +1188,6 @@ CGS_EXPORT int cgs_conv2d_nhwc_v7ws(const void* x, const void* x2, int C1, const
                                     const void* res, void* out, int N, int H, int W, int Cin, int Cout, int kh, int kw,
                                     int stride, int pad, int Ho, int Wo, int flags, void* ws, long long ws_bytes,
                                     hipStream_t stream) {
-  if (Cin % 32 || (x2 && (C1 % 32)) || Cout < 1 || (Cout % 8 && Cout > 16 && (Cin % 64 || (x2 && C1 % 64))))
-    return (int)hipErrorInvalidValue;
-  ConvArgs a{(const u16*)x, (const u16*)x2, (const u16*)w, (const u16*)bias, (const u16*)res, (u16*)out, N, H, W,
-             Cin, x2 ? C1 : Cin, Cout, kh, kw, stride, pad, Ho, Wo,
-             (bias ? EPI_BIAS : 0) | (res ? EPI_RESIDUAL : 0) | (flags & CONV_UP2X), 0, 1};
-  return conv_launch(a, stream, 7, ws, ws_bytes);
+  ConvArgs a = conv_args(x, x2, C1, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, flags);
+  return conv_shape_ok(a) ? conv_launch(a, stream, 7, ws, ws_bytes) : (int)hipErrorInvalidValue;
 }

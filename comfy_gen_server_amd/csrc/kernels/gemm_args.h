@@ -83,14 +83,6 @@ struct GemmArgs {
 // tile width 256 or 160)
 int gemm_w6(const GemmArgs& a, int dbg, int group_m, int grid_cap, int bn);
 
-// hipFuncAttributeMaxDynamicSharedMemorySize = bytes on Kern, once per process (before Kern's first launch)
-template <auto Kern>
-inline void max_dynamic_lds_once(int bytes) {
-  static const hipError_t set =
-      hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  (void)set;
-}
-
 // Launch a kernel whose parameters begin (A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, epi, alpha): the struct
 // expands into that prefix, tail follows it. Dynamic LDS is raised to lds_bytes first (max_dynamic_lds_once).
 template <auto Kern, typename... Tail>

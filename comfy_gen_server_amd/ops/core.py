@@ -973,7 +973,19 @@ def _upconv_use_taps(N, H, W, Cin, Cout, cached) -> bool:
     return cached and Cin >= 256 and Cout >= 32 and N * H * W * Cin * Cout * 36 >= (1 << 27)
 
 
-_FUSED_ACT_CONV = {"v3": 3, "v4": 4, "v8": 8}     # the mc::tile convs: their epilogue carries the activation
+# Autotune candidate name -> variant number of cgs_conv2d_nhwc_v / _act (conv.hip: conv_launch, conv_v3_launch)
+CONV_VARIANTS = {"v2": 2, "v3": 3, "v4": 4, "v5": 5, "v6": 6, "v7": 7, "v8": 8, "v6n128": 18, "v6w4": 21, "auto": -2}
+_FUSED_ACT_CONV = ("v3", "v4", "v8")     # the mc::tile convs: their epilogue carries the activation
+
+
+def _conv_operands(xc, x2c, w_nhwc, bias, res, out, kh, kw, stride, pad, flags):
+    """``(x, x2, C1, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, flags)``: the argument prefix
+    of cgs_conv2d_nhwc_v / _act / _gns / _v7ws for channels-last [N, C, H, W] operands (``x2c``, ``bias``, ``res``
+    may be None)."""
+    N, C1, H, W = xc.shape
+    _, Cout, Ho, Wo = out.shape
+    return (xc.data_ptr(), _ptr(x2c), C1, w_nhwc.data_ptr(), _ptr(bias), _ptr(res), out.data_ptr(), N, H, W,
+            C1 + (0 if x2c is None else x2c.shape[1]), Cout, kh, kw, stride, pad, Ho, Wo, flags)
 
 
 def _conv2d_act(x, weight, bias, stride, padding, residual, weight_nhwc, groups, upsample2x, x2, act, act_param):
@@ -1014,14 +1026,13 @@ def _conv2d_act(x, weight, bias, stride, padding, residual, weight_nhwc, groups,
         x2c = None if x2 is None else x2.contiguous(memory_format=torch.channels_last)
         r = None if residual is None else residual.contiguous(memory_format=torch.channels_last)
         out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-        _check(_lib().cgs_conv2d_nhwc_act(xc.data_ptr(), _ptr(x2c), C1, weight_nhwc.data_ptr(), _ptr(bias), _ptr(r),
-                                          out.data_ptr(), N, H, W, Cin, Cout, kh, kw, st, pd, Ho, Wo, flags,
+        _check(_lib().cgs_conv2d_nhwc_act(*_conv_operands(xc, x2c, weight_nhwc, bias, r, out, kh, kw, st, pd, flags),
                                           variant, ACT_CODES[act], act_param, _stream()), "cgs_conv2d_nhwc_act")
         return out
 
     # ("split" is timed last: whatever the first candidate of a tuning pass pays for a cold start, the form
     # that can never lose to conv + a separate activation pass does not pay it)
-    cands = [(n, (lambda v=v: fused(v))) for n, v in _FUSED_ACT_CONV.items()] + [("split", split)]
+    cands = [(n, (lambda v=CONV_VARIANTS[n]: fused(v))) for n in _FUSED_ACT_CONV] + [("split", split)]
     choice = autotune.choose(("conv", N, H, W, Cin, Cout, kh, st, pd, flags, int(residual is not None))
                              + ((("dual", C1),) if x2 is not None else ()) + ("act", act, act_param),
                              cands, default="split")
@@ -1029,7 +1040,7 @@ def _conv2d_act(x, weight, bias, stride, padding, residual, weight_nhwc, groups,
         return split()
     count("conv", "hip")
     count("act_fused", "hip")
-    return fused(_FUSED_ACT_CONV[choice])
+    return fused(CONV_VARIANTS[choice])
 
 
 def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, stride=1, padding=0,
@@ -1083,16 +1094,12 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
         def run(variant):
             out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=x.dtype,
                               memory_format=torch.channels_last)
+            pre = _conv_operands(xc, x2c, weight_nhwc, bias, r, out, kh, kw, stride, padding, flags)
             ws = _v7_ws(N * Ho * Wo, Cout, kh * kw * Cin, x.device) if variant == 7 else None
             if ws is not None:
-                _check(_lib().cgs_conv2d_nhwc_v7ws(xc.data_ptr(), _ptr(x2c), C1, weight_nhwc.data_ptr(), _ptr(bias),
-                                                   _ptr(r), out.data_ptr(), N, H, W, Cin, Cout, kh, kw, stride,
-                                                   padding, Ho, Wo, flags, ws.data_ptr(), ws.numel(), _stream()),
-                       "cgs_conv2d_nhwc_v7ws")
-                return out
-            _check(_lib().cgs_conv2d_nhwc_v(xc.data_ptr(), _ptr(x2c), C1, weight_nhwc.data_ptr(), _ptr(bias), _ptr(r),
-                                            out.data_ptr(), N, H, W, Cin, Cout, kh, kw, stride, padding, Ho, Wo,
-                                            flags, variant, _stream()), "cgs_conv2d_nhwc")
+                _check(_lib().cgs_conv2d_nhwc_v7ws(*pre, ws.data_ptr(), ws.numel(), _stream()), "cgs_conv2d_nhwc_v7ws")
+            else:
+                _check(_lib().cgs_conv2d_nhwc_v(*pre, variant, _stream()), "cgs_conv2d_nhwc")
             return out
 
         variant = -2            # process-wide override (cgs_conv_set_variant), default auto
@@ -1111,8 +1118,7 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
                     cands.append(("v6w4", lambda: run(21)))      # 128 x 80 tiles, 4 waves (batch-1 grids)
             choice = autotune.choose(("conv", N, H, W, Cin, Cout, kh, stride, padding, flags, int(r is not None))
                                      + ((("dual", C1),) if x2c is not None else ()), cands, default="auto")
-            variant = {"v2": 2, "v4": 4, "v5": 5, "v6": 6, "v7": 7, "v8": 8, "v6n128": 18, "v6w4": 21,
-                       "auto": -2}[choice]
+            variant = CONV_VARIANTS[choice]
         if (upsample2x and single and r is None and not gn_stats and kh == 3 and kw == 3 and stride == 1
                 and padding == 1 and Cout % 8 == 0 and weight.dtype == x.dtype
                 and _native.has_kernel("cgs_upconv_taps_nhwc")):
@@ -1133,9 +1139,9 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
                 and _native.has_kernel("cgs_conv2d_nhwc_gns")):
             out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
             part = torch.empty(N * (Ho * Wo // 64) * Cout * 2, device=x.device, dtype=torch.float32)
-            _check(_lib().cgs_conv2d_nhwc_gns(xc.data_ptr(), _ptr(x2c), C1, weight_nhwc.data_ptr(), _ptr(bias),
-                                              _ptr(r), out.data_ptr(), N, H, W, Cin, Cout, kh, kw, stride, padding,
-                                              Ho, Wo, flags, part.data_ptr(), _stream()), "cgs_conv2d_nhwc_gns")
+            _check(_lib().cgs_conv2d_nhwc_gns(*_conv_operands(xc, x2c, weight_nhwc, bias, r, out, kh, kw, stride,
+                                                              padding, flags), part.data_ptr(), _stream()),
+                   "cgs_conv2d_nhwc_gns")
             out._cgs_gnpart = (part, out.data_ptr())
             return out
         return run(variant)

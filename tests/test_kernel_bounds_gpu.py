@@ -1,8 +1,8 @@
 """Per-element error bounds (tests/_bounds.py) on the device for the bf16 GEMM, conv and attention kernels.
 
 Every case names one kernel and a shape inside that kernel's own dispatch domain, so the kernel of the test id is
-the one that runs (gemm_dispatch / conv_launch / flash_attn_dispatch fall through to another kernel outside it; no
-case relies on that). References are fp64 on the device. The shapes are the smallest that reach an edge: a single
+the one that runs (gemm_dispatch / conv_launch / flash_attn_dispatch fall through to another kernel outside it; only
+test_conv_bound_variant_fallback relies on that, to pin where the convs fall). References are fp64 on the device. The shapes are the smallest that reach an edge: a single
 partial tile, one row / one 8-wide vector past a full tile, the minimum K, an odd number of K steps, more tiles
 than a persistent kernel's workgroups, the workspace (split-K) paths. The guard tests place C with ldc = N + 8 in
 the middle of a pattern-filled buffer and require every element outside [0, M) x [0, N) to keep its bits; their
@@ -421,9 +421,10 @@ def test_gemm_bound_v7_split_tail_forms(cuda, form):
 
 
 # ------------------------------------------------------------------------------------------------ conv
-# conv_launch / conv_v3_launch (csrc/kernels/conv.hip): Cout <= 16 runs the narrow-output kernel whatever the
-# variant (2 excepted when Cin % 64 == 0); variant 2 needs Cin % 64; 3 / 4 / 8 take Cin % 32 and Cout % 8, > 16;
-# 5 adds Cin % 64 (and C1 % 64 with two sources); 6 / 7 add kh kw Cin >= 128; 18 adds Cout % 128; 21 Cout % 80.
+# conv_shape_ok / conv_launch / conv_variant_ok (csrc/kernels/conv.hip): Cout <= 16 runs the narrow-output kernel
+# whatever the variant (2 excepted when Cin % 64 == 0); variant 2 needs Cin % 64; 3 / 4 / 8 take Cin % 32 and
+# Cout % 8, > 16; 5 adds Cin % 64 (and C1 % 64 with two sources); 6 / 7 add kh kw Cin >= 128; 18 adds Cout % 128;
+# 21 Cout % 80. A forced variant outside its domain runs the 8-wave v3 tile (conv_v3_launch).
 # Case: (N, C1, C2, H, W, Cout, k, stride, pad, upsample2x). ops.conv2d reads x2 in the kernel only with
 # C1 % 64 == C2 % 64 == 0 and Cout % 8 == 0; every dual case here has that.
 def _conv_shapes(cin, cin_k1, cout):
@@ -482,6 +483,86 @@ def test_conv_bound(cuda, name, variant, N, C1, C2, H, W, Cout, k, s, p, up, epi
     st = ops.stats()
     assert st.get(("conv", "hip"), 0) == 1 and not any(key[1] == "lib" for key in st), st
     assert_within(y, ref, tol, f"conv/{name} {N}x{C1}+{C2}x{H}x{W}->{Cout} k{k}s{s} up={up} {epi}")
+
+
+@pytest.mark.parametrize("variant,Cin,k,p", [(5, 96, 3, 1), (6, 64, 1, 0), (7, 64, 1, 0), (18, 64, 3, 1), (21, 64, 3, 1)])
+def test_conv_bound_variant_fallback(cuda, variant, Cin, k, p):
+    """A forced variant outside its domain (conv_variant_ok: Cin % 64; K = 64 < 128 twice; Cout % 128; Cout % 80) runs
+    the 8-wave v3 tile, whose domain every case lies in, and stays inside conv_bound."""
+    lib = _native.load_kernels()
+    N, H, W, Cout = 3, 5, 7, 24
+    assert not _conv_in_domain(variant, Cin, 0, Cout, k) and _conv_in_domain(4, Cin, 0, Cout, k)
+    nhwc = lambda t: t.to(BF).contiguous(memory_format=torch.channels_last)
+    torch.manual_seed(0)
+    x = nhwc(torch.randn(N, Cin, H, W, device=cuda) + 0.5)
+    w = (torch.randn(Cout, Cin, k, k, device=cuda) / math.sqrt(Cin * k * k)).to(BF)
+    b = torch.randn(Cout, device=cuda).to(BF)
+    r = nhwc(torch.randn(N, Cout, H, W, device=cuda))
+    ref, tol = conv_bound(x, w, b, r, 1, p)
+    lib.cgs_conv_set_variant(variant)
+    try:
+        y = ops.conv2d(x, w, b, 1, p, residual=r, weight_nhwc=w.permute(0, 2, 3, 1).contiguous())
+    finally:
+        lib.cgs_conv_set_variant(-1)
+    st = ops.stats()
+    assert st.get(("conv", "hip"), 0) == 1 and not any(key[1] == "lib" for key in st), st
+    assert_within(y, ref, tol, f"conv/variant {variant} out of domain {N}x{Cin}x{H}x{W}->{Cout} k{k}")
+
+
+class _RefusedConv:
+    """Operands of one conv call that an entry must refuse: real tensors of the next legal shape (channel counts up to
+    a multiple of 64, 24 output channels), so even a launch would stay inside them; ``out`` holds a sentinel."""
+
+    def __init__(self, cuda, Cin, Cout, C1=None, k=3, HW=(5, 7)):
+        up64 = lambda c: (c + 63) // 64 * 64
+        nhwc = lambda *s: torch.zeros(s, device=cuda, dtype=BF).contiguous(memory_format=torch.channels_last)
+        H, W = HW
+        self.x = nhwc(1, up64(Cin if C1 is None else C1), H, W)
+        self.x2 = None if C1 is None else nhwc(1, up64(Cin - C1), H, W)
+        self.w = torch.zeros(24, k, k, up64(Cin), device=cuda, dtype=BF)
+        self.b = torch.zeros(24, device=cuda, dtype=BF)
+        self.r = nhwc(1, 24, H, W)
+        self.out = nhwc(1, 24, H, W).fill_(7.0)
+        self.gnp = torch.zeros(1 * (H * W + 63) // 64 * 24 * 2, device=cuda, dtype=torch.float32)
+        self.shape = (1, H, W, Cin, Cout, k, k, 1, k // 2, H, W)
+        self.C1 = Cin if C1 is None else C1
+
+    def dual(self):      # the operands of the entries that take x2, up to and including flags
+        return (self.x.data_ptr(), _ptr(self.x2), self.C1, self.w.data_ptr(), self.b.data_ptr(), self.r.data_ptr(),
+                self.out.data_ptr()) + self.shape + (0,)
+
+    def untouched(self):
+        torch.cuda.synchronize()
+        return bool((self.out == 7.0).all())
+
+
+def test_conv_entries_refuse_same_forms(cuda):
+    """conv_shape_ok: the four general entries return hipErrorInvalidValue for the same shapes and launch nothing.
+    cgs_conv2d_nhwc_gns refuses what it adds to the v6 domain."""
+    lib = _native.load_kernels()
+    s = core._stream()
+    entries = {"ex": lambda o: lib.cgs_conv2d_nhwc_ex(*o.dual(), s),
+               "v": lambda o: lib.cgs_conv2d_nhwc_v(*o.dual(), -2, s),
+               "v7ws": lambda o: lib.cgs_conv2d_nhwc_v7ws(*o.dual(), None, 0, s),
+               "nhwc": lambda o: lib.cgs_conv2d_nhwc(o.x.data_ptr(), o.w.data_ptr(), o.b.data_ptr(), o.r.data_ptr(),
+                                                     o.out.data_ptr(), *o.shape, s)}
+    single = [dict(Cin=48, Cout=24), dict(Cin=64, Cout=0), dict(Cin=96, Cout=20)]
+    dual = [dict(Cin=96, Cout=24, C1=48), dict(Cin=128, Cout=20, C1=32)]
+    lib.cgs_conv_set_variant(-1)
+    try:
+        for name, call in entries.items():
+            for form in single + (dual if name != "nhwc" else []):
+                o = _RefusedConv(cuda, **form)
+                assert call(o) == 1, (name, form)
+                assert o.untouched(), (name, form)
+        gns = lambda o, gnp: lib.cgs_conv2d_nhwc_gns(*o.dual(), gnp, s)
+        for form, with_gnp in [(dict(Cin=64, HW=(16, 16)), False), (dict(Cin=96, HW=(16, 16)), True),
+                               (dict(Cin=64, k=1, HW=(16, 16)), True), (dict(Cin=64, HW=(5, 7)), True)]:
+            o = _RefusedConv(cuda, Cout=24, **form)
+            assert gns(o, o.gnp.data_ptr() if with_gnp else None) == 1, ("gns", form, with_gnp)
+            assert o.untouched(), ("gns", form)
+    finally:
+        lib.cgs_conv_set_variant(-1)
 
 
 @pytest.mark.parametrize("C1,C2,s,up", [(320, 0, 1, False), (320, 0, 2, False), (320, 0, 1, True), (256, 64, 1, False)])
