@@ -109,6 +109,48 @@ tome_match, s = (a_i . b_j) inv_a inv_b with inv = rsqrtf(sum of squares):
   the dot product runs over k in sequence, two more products; the second term is the two reciprocal roots (the
   relative error of their sums of squares, (ceil(C / 64) + 7) e each, is not itemised: for C >= 32 the second half
   of C_ACC (C + 2) e mag, unused by a sequential sum, majorises it). A row of zeros has inv = 0 and s = 0.
+
+The fused epilogues (test_epilogue_bounds_gpu.py). Activation epilogues of the GEMMs and convs, out = round(act(pre))
+(+ res), pre = alpha a w^T + bias (or the LayerNorm-folded or conv pre-activation), d_pre = C_ACC K e mag as above:
+  tol = u |ref| (1 + 2u) + ([res] u |act(pre)| + slope_act d_pre + act_err) (1 + u)
+  [res] u |act(pre)|: the mc::tile kernels round the activated tile to bf16 and add the residual to that (mfma_core.h,
+    the row-wise read-back loop); v6, skinny and the split-K reduce add it in fp32 and round once, inside the same term.
+  slope_act = max |act'|: GELU_SLOPE (erf and tanh GELU), SILU_SLOPE (SiLU; quick-GELU is the same curve in 1.702 x,
+    with 1.702 x as the argument the slope in x is the same number), 1 (ReLU), max(1, |p|) (leaky ReLU).
+  act_err: erf path GELU_ABS (gelu_sig against the exact function). SIG family, x rcp(1 + exp2(t)), t = x fma(x x, b,
+    a) (act_fam / act_fam2, common.h): the fp32 constants a, b are within e of -c0 log2 e, -c1 log2 e; x x, the fma and
+    the product x q round once each: |dt| <= 4 e |t| (a and b have one sign, so |t| = |x| (|a| + |b| x^2)); z = t ln 2 is
+    the sigmoid's argument, so exp2 is off by 4 e |z| relative, then EXP2_REL, the addition of 1 (e), RCP_REL, the final
+    product (e); the error of the denominator is at most that of its exp term:
+      act_err = (4 |z| e + EXP2_REL + RCP_REL + 2 e) |act(pre)| + 1e-36   (1e-36: exp2 overflows to rcp(inf) = 0)
+    LIN family: one rounding of a x, e |act(pre)| (x >= 0 and relu are exact).
+  (1 + u): the last store rounds a value within those terms of ref (as _store_dt).
+Row-statistics partials (pq::run RSO, mfma_pp160.h), (mean, M2) of every 80-column chunk of a stored row. Lane fq of
+the four that hold a row's chunk has 20 values: columns 8 fq .. + 7, 32 + 8 fq .. + 7, 64 + 4 fq .. + 3 (colj); it sums
+d = v - sh, sh = its first value, as five trees of four (depth 2) added in sequence (5): Lb = 7 dependent additions.
+  lane:  s1 off by (Lb + 1) e S, S = sum |d| (the rounding of d);  s2 by (Lb + 2) e s2
+         dmean = (Lb + 3) e S / 20 + e |mean|       the product by fl(1 / 20) (2 e) and the addition of sh
+         dM2   = (3 Lb + 7) e s2                    m2 = s2 - s1^2 / 20 cancels at the magnitude of s2: s1^2 / 20 <= s2
+                                                    (Cauchy-Schwarz), 2 (Lb + 1) e s2 from s1, 2 e s2 from its two
+                                                    products, e s2 from the subtraction, (Lb + 2) e s2 from s2
+  merge of two halves of n values (lanes l ^ 16, then l ^ 32): mean = (ma + mb) / 2, m2 = qa + qb + d^2 n / 2, d = mb - ma,
+         delta = dma + dmb:  dmean = delta / 2 + e |mean|
+         dM2 = dqa + dqb + n |d| delta + n delta^2 / 2 + 4 e d^2 n / 2 + 2 e m2     d, d d and the product by n / 2
+                                                    (two roundings on d^2), then two additions of positive terms
+  |y| is known, so every term is evaluated on the data. The sum of a representable x and an increment is off by at
+  most the increment, so the two e |mean| are min(e |mean|, S / 20) in the lane (sh + s1 / 20) and min(e |mean|,
+  (|d| + delta) / 2) in a merge (ma + mb = 2 ma + d): a chunk of identical values has d = S = s2 = 0 in every lane
+  and every merge, and tol(M2) = tiny(fp32) alone.
+  partials_merge_tol: partials each within (dm_p, dq_p) of exact ones move the row's mean = mean_p m_p by mean_p dm_p
+  =: dmean and its M2 = sum q_p + 80 sum (m_p - mean)^2 by sum dq_p + 80 sum (2 |m_p - mean| dd_p + dd_p^2), dd_p =
+  dm_p + dmean; rstd by rstd dM2 / (2 n (var + eps)). Added to layernorm_stats_bound of the stored rows and to the
+  merge's own rs_from_partials_bound it bounds cgs_ln_rs_from_partials of a producer's partials against the rows.
+Sum-of-squares partials (pq::run GNS == 2), [M / 64, N] over the 64 rows of a wave: NI = 4 additions in sequence, then
+row16_sum (4): L = 8; positive terms only, tol = C_ACC (L + 1) e ref (+ 1: the square) + 64 tiny(fp32) (each of the
+64 squares may be flushed below 2^-126). A block of zeros is exact.
+GroupNorm partials (pq::run GNS == 1), [N, HW / 64, C, 2], two passes over the wave's registers: the sum of 4 values in
+sequence (3) and row16_sum (4), L = 7, the product by 1 / 64 is exact; the structure is _ln_stats's:
+  dmean = C_ACC L e mean |v| + e |mean|;  dM2 = C_ACC (L + 4) e M2 + 64 dmean^2    (v - m, its square, 8 additions)
 """
 import math
 
@@ -205,18 +247,75 @@ def geglu_bound(a, w, bias=None, K=None):
     return _geglu_tol(x1, g, C_ACC * K * E * m1, C_ACC * K * E * mg)
 
 
+def _lnfold_pre_mag(a, w2, b2, rs, cs):
+    """(pre, mag) of rstd (a w2^T - mean cs) + b2 (lnfold_bound); mag also takes |rstd mean cs|."""
+    a, w2, b2, rs, cs = f64(a), f64(w2), f64(b2), f64(rs), f64(cs)
+    mu, rstd = rs[:, :1], rs[:, 1:2]
+    pre = rstd * (a @ w2.t() - mu * cs[None, :])
+    mag = rstd.abs() * (a.abs() @ w2.abs().t()) + (rstd * mu * cs[None, :]).abs()
+    if b2 is not None:
+        pre = pre + b2
+        mag = mag + b2.abs()
+    return pre, mag
+
+
+# the sigmoid's argument z of the SIG family, act = x sigmoid(z(x))
+_SIG_ARG = {"gelu_tanh": lambda x: 2 * math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3), "quick_gelu": lambda x: 1.702 * x,
+            "silu": lambda x: x}
+
+
+def act_ref(pre, act, param=0.0):
+    """The activation set of the fused epilogues (CgsAct, csrc/kernels/common.h) in fp64; ``act`` None: the identity;
+    ``param``: the leaky_relu slope, taken as the fp32 value the kernel is passed."""
+    pre = f64(pre)
+    if act is None:
+        return pre
+    if act == "gelu":
+        return F.gelu(pre)
+    if act in _SIG_ARG:
+        return pre * torch.sigmoid(_SIG_ARG[act](pre))
+    if act == "relu":
+        return pre.clamp_min(0.0)
+    assert act == "leaky_relu", act
+    return torch.where(pre >= 0, pre, pre * _f32(param))
+
+
+def _act_tol(pre, d_pre, res, act, param):
+    """(ref, tol) of round(act(pre)) (+ res) for a pre-activation within d_pre of pre (module docstring)."""
+    y = act_ref(pre, act, param)
+    if act is None:
+        slope, err = 1.0, 0.0
+    elif act == "gelu":
+        slope, err = GELU_SLOPE, GELU_ABS
+    elif act in _SIG_ARG:
+        slope = GELU_SLOPE if act == "gelu_tanh" else SILU_SLOPE
+        err = (4 * _SIG_ARG[act](pre).abs() * E + EXP2_REL + RCP_REL + 2 * E) * y.abs() + 1e-36
+    else:
+        slope = 1.0 if act == "relu" else max(1.0, abs(_f32(param)))
+        err = E * y.abs() if act == "leaky_relu" else 0.0
+    ref, d = y, slope * d_pre + err
+    if res is not None:
+        ref = y + f64(res)
+        d = d + U * y.abs()
+    return ref, _store(ref) + d * (1 + U)
+
+
+def gemm_act_bound(a, w, bias, res, act, param=0.0, alpha=1.0, K=None, rs=None, cs=None):
+    """out = round(act(alpha a w^T + bias)) (+ res); with rs / cs the pre-activation is lnfold_bound's (w = w2, bias =
+    b2, alpha ignored). The fp32 addition of the residual is part of mag, as in gemm_bound."""
+    K = a.shape[-1] if K is None else K
+    pre, mag = _pre_mag(a, w, bias, alpha) if rs is None else _lnfold_pre_mag(a, w, bias, rs, cs)
+    if res is not None:
+        mag = mag + f64(res).abs()
+    return _act_tol(pre, C_ACC * K * E * mag, res, act, param)
+
+
 def lnfold_bound(a, w2, b2, rs, cs, geglu=False):
     """The LayerNorm-folded GEMM from the operands the kernel is given: out = rstd (a w2^T - mean cs) + b2, with
     rs [M, 2] = (mean, rstd) per row, w2 = W gamma (bf16), cs = rowsum(w2) (fp32), b2 (bf16). Judges the kernel's
     arithmetic only; mag also takes |rstd mean cs|. geglu: w2 / cs / b2 in the plain row order."""
     K = a.shape[-1]
-    a, w2, b2, rs, cs = f64(a), f64(w2), f64(b2), f64(rs), f64(cs)
-    mu, rstd = rs[:, :1], rs[:, 1:2]
-    ref = rstd * (a @ w2.t() - mu * cs[None, :])
-    mag = rstd.abs() * (a.abs() @ w2.abs().t()) + (rstd * mu * cs[None, :]).abs()
-    if b2 is not None:
-        ref = ref + b2
-        mag = mag + b2.abs()
+    ref, mag = _lnfold_pre_mag(a, w2, b2, rs, cs)
     if geglu:
         (x1, g), (m1, mg) = ref.chunk(2, dim=-1), mag.chunk(2, dim=-1)
         return _geglu_tol(x1, g, C_ACC * K * E * m1, C_ACC * K * E * mg)
@@ -224,9 +323,9 @@ def lnfold_bound(a, w2, b2, rs, cs, geglu=False):
 
 
 # ------------------------------------------------------------------------------------------------ conv
-def conv_bound(x, w, bias=None, res=None, stride=1, pad=0, upsample2x=False, x2=None):
-    """out = conv2d(x (cat x2) (nearest 2x), w) + bias + res in NCHW; K = Cin kh kw."""
-    x, w, bias, res = f64(x), f64(w), f64(bias), f64(res)
+def _conv_pre_mag(x, w, bias, stride, pad, upsample2x, x2):
+    """(pre, mag, K) of conv2d(x (cat x2) (nearest 2x), w) + bias in NCHW; K = Cin kh kw."""
+    x, w, bias = f64(x), f64(w), f64(bias)
     if x2 is not None:
         x = torch.cat([x, f64(x2)], 1)
     if upsample2x:
@@ -234,6 +333,22 @@ def conv_bound(x, w, bias=None, res=None, stride=1, pad=0, upsample2x=False, x2=
     K = w.shape[1] * w.shape[2] * w.shape[3]
     pre = F.conv2d(x, w, bias, stride, pad)
     mag = F.conv2d(x.abs(), w.abs(), None if bias is None else bias.abs(), stride, pad)
+    return pre, mag, K
+
+
+def conv_act_bound(x, w, bias, res, act, param=0.0, stride=1, pad=0, upsample2x=False, x2=None):
+    """out = round(act(conv2d(x (cat x2) (nearest 2x), w) + bias)) (+ res) in NCHW: gemm_act_bound on conv_bound's
+    pre-activation."""
+    pre, mag, K = _conv_pre_mag(x, w, bias, stride, pad, upsample2x, x2)
+    if res is not None:
+        mag = mag + f64(res).abs()
+    return _act_tol(pre, C_ACC * K * E * mag, res, act, param)
+
+
+def conv_bound(x, w, bias=None, res=None, stride=1, pad=0, upsample2x=False, x2=None):
+    """out = conv2d(x (cat x2) (nearest 2x), w) + bias + res in NCHW; K = Cin kh kw."""
+    pre, mag, K = _conv_pre_mag(x, w, bias, stride, pad, upsample2x, x2)
+    res = f64(res)
     ref, tol = pre, 0.0
     if res is not None:
         ref = pre + res
@@ -431,6 +546,78 @@ def rs_from_partials_bound(part, eps):
     rstd = 1 / torch.sqrt(var + eps)
     drstd = rstd * (0.5 * dm2 / (80 * P) / (var + eps) + RSQRT_REL)
     return torch.cat([mean, rstd], -1), torch.cat([dmean, drstd], -1) + TINY[torch.float32]
+
+
+def partials_merge_tol(part, tol, eps):
+    """[M, 2]: how far the (mean, rstd) that part [M, P, 2] stands for move when every partial moves within tol
+    [M, P, 2]: mean = mean_p m_p, M2 = sum q_p + 80 sum (m_p - mean)^2, to second order in the means' errors;
+    drstd = rstd dM2 / (2 n (var + eps))."""
+    part, tol = f64(part), f64(tol)
+    m, q, dm, dq = part[..., 0], part[..., 1], tol[..., 0], tol[..., 1]
+    n = 80 * m.shape[1]
+    mean, dmean = m.mean(-1, keepdim=True), dm.mean(-1, keepdim=True)
+    dev, dd = (m - mean).abs(), dm + dmean
+    m2 = q.sum(-1, keepdim=True) + 80 * (dev ** 2).sum(-1, keepdim=True)
+    dm2 = dq.sum(-1, keepdim=True) + 80 * (2 * dev * dd + dd ** 2).sum(-1, keepdim=True)
+    var = m2 / n
+    return torch.cat([dmean, 0.5 * dm2 / n / (var + eps) / torch.sqrt(var + eps)], -1)
+
+
+RSO_LB = 7              # five trees of four (2) added in sequence (5): the lane sums of pq::run RSO
+# the 20 columns of an 80-column chunk that lane fq of a row's four holds (colj, mfma_pp160.h), its first value first
+RSO_LANE_COLS = [[32 * p + 8 * fq + t for p in (0, 1) for t in range(8)] + [64 + 4 * fq + t for t in range(4)]
+                 for fq in range(4)]
+
+
+def rowstats_partials_bound(y):
+    """The fp32 (mean, M2) [M, N / 80, 2] of every 80-column chunk of every row of the stored y [M, N] (pq::run RSO):
+    judges the statistics arithmetic only (module docstring)."""
+    y = f64(y)
+    M, N = y.shape
+    assert N % 80 == 0, N
+    v = y.reshape(M, N // 80, 80)
+    idx = torch.tensor(RSO_LANE_COLS, device=y.device)
+    lv = v[..., idx]                                          # [M, P, 4 lanes, 20]
+    d = lv - lv[..., :1]
+    S, s2 = d.abs().sum(-1), (d * d).sum(-1)
+    mean = lv.mean(-1)
+    q = ((lv - mean[..., None]) ** 2).sum(-1)
+    dmean = (RSO_LB + 3) * E * S / 20 + torch.minimum(E * mean.abs(), S / 20)
+    dq = (3 * RSO_LB + 7) * E * s2
+    n = 20
+    while mean.shape[-1] > 1:                                 # lanes l ^ 16 (fq 0-1, 2-3), then l ^ 32
+        ma, mb, qa, qb = mean[..., 0::2], mean[..., 1::2], q[..., 0::2], q[..., 1::2]
+        dd, delta = (mb - ma).abs(), dmean[..., 0::2] + dmean[..., 1::2]
+        mean = 0.5 * (ma + mb)
+        q = qa + qb + dd * dd * (n / 2)
+        dmean = 0.5 * delta + torch.minimum(E * mean.abs(), 0.5 * (dd + delta))
+        dq = dq[..., 0::2] + dq[..., 1::2] + n * dd * delta + 0.5 * n * delta ** 2 + 4 * E * dd * dd * (n / 2) + 2 * E * q
+        n *= 2
+    ref = torch.cat([mean, q], -1)
+    return ref, torch.cat([dmean, dq], -1) + TINY[torch.float32]
+
+
+def sumsq_partials_bound(y, hw):
+    """The fp32 sums of squares [M / 64, N] of the stored y [M, N] over each 64-row block (pq::run GNS == 2); hw = rows
+    per image, a multiple of 64, so block m / 64 of the tensor is block (m % hw) / 64 of image m / hw."""
+    y = f64(y)
+    M, N = y.shape
+    assert hw % 64 == 0 and M % hw == 0, (M, hw)
+    ref = (y * y).reshape(M // 64, 64, N).sum(1)
+    return ref, torch.where(ref == 0, 0.0, C_ACC * (8 + 1) * E * ref + 64 * TINY[torch.float32])
+
+
+def gn_partials_bound(y_nhwc):
+    """The fp32 (mean, M2) [N, HW / 64, C, 2] of each 64-pixel block of the stored y [N, ..., C] (pq::run GNS == 1)."""
+    y = f64(y_nhwc)
+    N, C = y.shape[0], y.shape[-1]
+    v = y.reshape(N, -1, 64, C)
+    L = 7
+    mean = v.mean(2)
+    m2 = ((v - mean[:, :, None]) ** 2).sum(2)
+    dmean = C_ACC * L * E * v.abs().mean(2) + E * mean.abs()
+    dm2 = C_ACC * (L + 4) * E * m2 + 64 * dmean ** 2
+    return torch.stack([mean, m2], -1), torch.stack([dmean, dm2], -1) + TINY[torch.float32]
 
 
 def affine_layernorm_bound(x, scale, shift, add, eps, xa):

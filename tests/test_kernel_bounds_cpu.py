@@ -5,21 +5,24 @@ of the older kernel tests -- is rejected by assert_within. The norm, depthwise a
 bf16 and fp16 against emulations of the kernels' own algorithms (shifted block sums and Chan merges for GroupNorm,
 two passes for LayerNorm). The GRN family and the planar image-space kernels (upfirdn2d, fused_bias_act, resize,
 softmax_rows, tome_match) follow at the end: an emulation of each kernel's own slice, merge and tap structure, and
-the faults its older tests could not see."""
+the faults its older tests could not see. Last, the fused epilogues: the activation set behind the GEMM and conv
+epilogues from the kernel's own constants, and the statistics partials a producer writes beside its output (row
+statistics, sums of squares, GroupNorm partials) in the lane and register order of mfma_pp160.h."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from _bounds import (FBA_SHAPES, GRN_GNS_SHAPES, GRN_V2_SHAPES, RESIZE_CASES, RESIZE_MODES, SMR_COLS, SMR_ROWS,
-                     TOME_SHAPES, UPFIRDN_CFGS, UPFIRDN_KERNELS, affine_layernorm_bound, assert_tome,
-                     assert_within, attention_bound, conv_bound, dwconv_bound, fused_bias_act_bound, geglu_bound,
-                     gemm_bound, grn_apply_bound, grn_bound, grn_depth, grn_inputs, grn_nx, grn_row_tiled,
-                     grn_scale_weight_bound, grn_slices, grn_stats_bound, groupnorm_apply_bound, groupnorm_bound,
-                     groupnorm_stats_bound, layernorm_bound, layernorm_stats_bound, lnfold_bound, rel, resize_bound,
-                     resize_coords, rs_from_partials_bound, smr_inputs, softmax2_bound, softmax_rows_bound, tome_inputs,
-                     upfirdn2d_bound, upfirdn_kernel)
+from _bounds import (FBA_SHAPES, GRN_GNS_SHAPES, GRN_V2_SHAPES, RESIZE_CASES, RESIZE_MODES, RSO_LANE_COLS, SMR_COLS,
+                     SMR_ROWS, TOME_SHAPES, UPFIRDN_CFGS, UPFIRDN_KERNELS, affine_layernorm_bound, assert_tome,
+                     assert_within, attention_bound, conv_act_bound, conv_bound, dwconv_bound, fused_bias_act_bound,
+                     geglu_bound, gemm_act_bound, gemm_bound, gn_partials_bound, grn_apply_bound, grn_bound, grn_depth,
+                     grn_inputs, grn_nx, grn_row_tiled, grn_scale_weight_bound, grn_slices, grn_stats_bound,
+                     groupnorm_apply_bound, groupnorm_bound, groupnorm_stats_bound, layernorm_bound,
+                     layernorm_stats_bound, lnfold_bound, partials_merge_tol, rel, resize_bound, resize_coords,
+                     rowstats_partials_bound, rs_from_partials_bound, smr_inputs, softmax2_bound, softmax_rows_bound,
+                     sumsq_partials_bound, tome_inputs, upfirdn2d_bound, upfirdn_kernel)
 
 BF = torch.bfloat16
 DTYPES = [torch.bfloat16, torch.float16]
@@ -1026,3 +1029,243 @@ def test_tome_emulation_and_faults(B, Na, Nb, C, dtype):
     if Nb > 1:
         with pytest.raises(AssertionError, match="higher index"):
             assert_tome(*_emulate_tome(a, b, high_tie=True), a, b, what + ": ties to the higher index")
+
+
+# ------------------------------------------------------------------------------------------------ fused epilogues
+# a / b of act_family (csrc/kernels/common.h): -c0 log2 e, -c1 log2 e of x sigmoid(x (c0 + c1 x^2))
+ACT_AB = {"gelu_tanh": (-2.302208198e+00, -1.029432396e-01), "quick_gelu": (-2.455466953e+00, 0.0),
+          "silu": (-1.442695041e+00, 0.0)}
+ACT_CASES = [(None, 0.0), ("gelu", 0.0), ("gelu_tanh", 0.0), ("quick_gelu", 0.0), ("silu", 0.0), ("relu", 0.0),
+             ("leaky_relu", 0.2), ("leaky_relu", -0.3)]
+
+
+def _emulate_act(x, act, param=0.0):
+    """act_fam in fp32: gelu_sig; x * rcp(1 + exp2(x * fma(x * x, b, a))); x >= 0 ? x : a * x."""
+    if act is None:
+        return x
+    if act == "gelu":
+        return _gelu_sig(x)
+    if act in ACT_AB:
+        a, b = ACT_AB[act]
+        return x * (1.0 / (1.0 + torch.exp2(x * ((x * x) * b + a))))
+    if act == "relu":
+        return x.clamp_min(0.0)
+    return torch.where(x >= 0, x, x * torch.tensor(param, dtype=torch.float32))
+
+
+def _act_inputs(M, N, K, seed=0):
+    """_gemm_inputs with eight pre-activation columns pushed to +-9 through the bias: the clamp of gelu_sig at +-8 and
+    the saturated sigmoid."""
+    a, w, b, r = _gemm_inputs(M, N, K, seed)
+    b[:4], b[4:8] = 9.0, -9.0
+    return a, w, b, r
+
+
+def _emulate_gemm_act(a, w, b, r, act, param=0.0, two_roundings=True, after_res=False):
+    """round(act(a w^T + b)) (+ r): the mc::tile kernels round, add r to the bf16 tile and round again; v6, skinny and
+    the split-K reduce add r in fp32. after_res: the fault act(pre + r)."""
+    pre = a.float() @ w.float().t() + b.float()
+    if after_res:
+        return _emulate_act(pre + r.float(), act, param).to(BF)
+    y = _emulate_act(pre, act, param)
+    if r is None:
+        return y.to(BF)
+    return (y.to(BF).float() + r.float()).to(BF) if two_roundings else (y + r.float()).to(BF)
+
+
+@pytest.mark.parametrize("act,param", ACT_CASES)
+@pytest.mark.parametrize("M,N,K", [(33, 40, 32), (129, 136, 192), (257, 168, 640)])
+def test_gemm_act_emulation_within_bound(M, N, K, act, param):
+    a, w, b, r = _act_inputs(M, N, K)
+    pre = a.double() @ w.double().t() + b.double()
+    assert bool((pre[:, :4] > 8).any()) and bool((pre[:, 4:8] < -8).any())      # both sides of gelu_sig's clamp
+    for res in (None, r):
+        ref, tol = gemm_act_bound(a, w, b, res, act, param)
+        for two in ((False, True) if res is not None else (False,)):
+            assert_within(_emulate_gemm_act(a, w, b, res, act, param, two), ref, tol,
+                          f"emulated gemm {M}x{N}x{K} {act}({param}) res={res is not None} two roundings={two}")
+    if act is None:                                          # the identity is gemm_bound's own case
+        ref0, tol0 = gemm_bound(a, w, b, r)
+        assert torch.equal(ref, ref0) and bool((tol >= tol0).all()) and bool((tol <= tol0 * 1.01).all())
+
+
+def test_gemm_act_bound_lnfold_and_conv():
+    """The two other pre-activations: the LayerNorm fold (rs / cs) and conv_bound's."""
+    M, N, K = 70, 96, 128
+    a, w, b, _ = _act_inputs(M, N, K, seed=1)
+    x = (a.float() * 3 + 1.5).to(BF)
+    rs = torch.stack([x.float().mean(1), torch.rsqrt(x.float().var(1, unbiased=False) + 1e-5)], 1)
+    cs = w.float().sum(1)
+    pre = rs[:, 1:2] * (x.float() @ w.float().t() - rs[:, :1] * cs[None]) + b.float()
+    ref, tol = gemm_act_bound(x, w, b, None, "gelu", rs=rs, cs=cs)
+    assert_within(_gelu_sig(pre).to(BF), ref, tol, "emulated lnfold + gelu")
+    _rejected(pre.to(BF), ref, tol, "lnfold + gelu: activation skipped")
+    ref0, tol0 = lnfold_bound(x, w, b, rs, cs)
+    ref1, tol1 = gemm_act_bound(x, w, b, None, None, rs=rs, cs=cs)
+    assert torch.equal(ref0, ref1) and bool((tol1 >= tol0).all())
+    g, xc, x2, wc, bc = _conv_inputs(2, 24, 8, 9, 8, 24)
+    bc[:2], bc[2:4] = 9.0, -9.0
+    cat = torch.cat([xc, x2], 1).float()
+    for act, param in ACT_CASES:
+        for stride, up in ((1, False), (2, False), (1, True)):
+            xin = F.interpolate(cat, scale_factor=2.0, mode="nearest") if up else cat
+            pre = F.conv2d(xin, wc.float(), bc.float(), stride, 1)
+            res = torch.randn(pre.shape, generator=g).to(BF) if not up else None
+            y = _emulate_act(pre, act, param).to(BF)
+            y = (y.float() + res.float()).to(BF) if res is not None else y
+            ref, tol = conv_act_bound(xc, wc, bc, res, act, param, stride, 1, upsample2x=up, x2=x2)
+            assert_within(y, ref, tol, f"emulated conv {act}({param}) s{stride} up={up}")
+    ref, tol = conv_act_bound(xc, wc, bc, None, "leaky_relu", 0.2, 1, 1, x2=x2)
+    _rejected(F.conv2d(cat, wc.float(), bc.float(), 1, 1).clamp_min(0).to(BF), ref, tol, "conv: leaky slope 0")
+    ref0, tol0 = conv_bound(xc, wc, bc, None, 1, 1, x2=x2)                 # the identity is conv_bound's own case
+    ref1, tol1 = conv_act_bound(xc, wc, bc, None, None, 0.0, 1, 1, x2=x2)
+    assert torch.equal(ref0, ref1) and bool((tol1 >= tol0).all()) and bool((tol1 <= tol0 * 1.01).all())
+
+
+SIG_SET = ["gelu", "gelu_tanh", "quick_gelu", "silu"]
+
+
+@pytest.mark.parametrize("res", [False, True])
+def test_gemm_act_faults(res):
+    M, N, K = 257, 136, 96                                   # bm + 1, bn + 8 of the 256 x 128 tiles
+    a, w, b, r = _act_inputs(M, N, K)
+    r = r if res else None
+    for want in SIG_SET:                                     # another member of the set, pairwise
+        ref, tol = gemm_act_bound(a, w, b, r, want)
+        for got in SIG_SET:
+            if got != want:
+                _rejected(_emulate_gemm_act(a, w, b, r, got), ref, tol, f"{want} asked, {got} applied")
+    ref, tol = gemm_act_bound(a, w, b, r, "leaky_relu", 0.2)
+    _rejected(_emulate_gemm_act(a, w, b, r, "relu"), ref, tol, "leaky_relu(0.2): slope 0")
+    if res:
+        for act, param in ACT_CASES[1:]:
+            ref, tol = gemm_act_bound(a, w, b, r, act, param)
+            _rejected(_emulate_gemm_act(a, w, b, r, act, param, after_res=True), ref, tol, f"{act} after the residual")
+    # the same faults in the last row's last vector only: under the Frobenius-norm threshold of the older tests (the
+    # two GELUs are within 5e-4 of each other, over a bf16 ulp only where -3 < x < -1.5: eight values need not hold one,
+    # so that pair is judged on the whole matrix above; so is the activation after the residual, which moves eight
+    # values of a matrix this small by enough to show in the norm)
+    for want, param, got in [("quick_gelu", 0.0, "silu"), ("silu", 0.0, "gelu_tanh"), ("gelu_tanh", 0.0, "silu"),
+                             ("gelu", 0.0, "quick_gelu"), ("leaky_relu", 0.2, "relu")]:
+        ref, tol = gemm_act_bound(a, w, b, r, want, param)
+        y = _emulate_gemm_act(a, w, b, r, want, param)
+        y[-1, -8:] = _emulate_gemm_act(a, w, b, r, got)[-1, -8:]
+        assert rel(y, ref) < 4e-3
+        _rejected(y, ref, tol, f"{want} asked, {got} in the last vector of the last row")
+
+
+# ---- row-statistics partials (pq::run RSO)
+def _emulate_rowstats(y, shifted=True, drop_lane=False):
+    """fp32 (mean, M2) [M, N / 80, 2] as the RSO epilogue forms them: per lane 20 values shifted by its first, five
+    trees of four added in sequence, m2 = s2 - s1^2 / 20; then the merges with lane ^ 16 and lane ^ 32. Faults:
+    shifted=False (sh = 0), drop_lane (lane 1's values never enter: lane 0 merges with itself)."""
+    M, N = y.shape
+    lv = y.float().reshape(M, N // 80, 80)[..., torch.tensor(RSO_LANE_COLS)]           # [M, P, 4, 20]
+    sh = lv[..., :1] if shifted else torch.zeros_like(lv[..., :1])
+    d = (lv - sh).reshape(M, N // 80, 4, 5, 4)
+    s1, s2 = torch.zeros(M, N // 80, 4), torch.zeros(M, N // 80, 4)
+    for j in range(5):
+        d0, d1, d2, d3 = d[..., j, :].unbind(-1)
+        s1 = s1 + ((d0 + d1) + (d2 + d3))
+        s2 = s2 + ((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3))
+    i20 = torch.tensor(1.0 / 20.0, dtype=torch.float32)
+    mean, m2 = sh[..., 0] + s1 * i20, (s2 - s1 * s1 * i20).clamp_min(0.0)
+    if drop_lane:
+        mean[..., 1], m2[..., 1] = mean[..., 0], m2[..., 0]
+    for n in (20.0, 40.0):
+        ma, mb = mean[..., 0::2], mean[..., 1::2]
+        dd = mb - ma
+        mean, m2 = 0.5 * (ma + mb), m2[..., 0::2] + m2[..., 1::2] + dd * dd * (0.5 * n)
+    return torch.cat([mean, m2], -1)
+
+
+@pytest.mark.parametrize("mean", [0.5, 40.0])
+@pytest.mark.parametrize("P", [2, 4])
+def test_rowstats_partials_emulation_and_faults(P, mean):
+    """With the +-48 spikes of _ln_inputs in the first and last column the first lane of a row is shifted by an outlier:
+    its s2 is as large as an unshifted one and the bound says so. The unshifted fault is planted on the data without
+    them, where the shift keeps s2 at the spread."""
+    for spike in (SPIKE, 0.0):
+        y, _, _ = _ln_inputs(65, 80 * P, BF, mean=mean, spike=spike)
+        y[3] = y[3, 0]                                       # a row of identical values: M2 exact up to tiny
+        y[4, :80] = y[4, 5]
+        ref, tol = rowstats_partials_bound(y)
+        assert bool((ref[3, :, 1] == 0).all()) and tol[3, :, 1].max().item() < 1e-37 and tol[4, 0, 1].item() < 1e-37
+        assert (ref - _partials(y, P).double()).abs().max().item() < 1e-3 * max(1.0, mean)
+        what = f"rowstats partials P={P} mean {mean} spike {spike}"
+        part = _emulate_rowstats(y)
+        assert_within(part, ref, tol, "emulated " + what)
+        _rejected(part.flip(1), ref, tol, what + ": chunks swapped")
+        _rejected(_emulate_rowstats(y, drop_lane=True), ref, tol, what + ": one lane left out of the merge")
+        if mean == 40.0 and not spike:
+            _rejected(_emulate_rowstats(y, shifted=False), ref, tol, what + ": unshifted one-pass M2")
+    # the merged statistics: inside rs_from_partials_bound, and inside the row's own bound widened by the partials' tol
+    rs = _emulate_rs_from_partials(part, 1e-5)
+    r1, t1 = rs_from_partials_bound(part, 1e-5)
+    assert_within(rs, r1, t1, what + ": rs from the emulated partials")
+    r2, t2 = layernorm_stats_bound(y, 1e-5)
+    assert_within(rs, r2, t2 + t1 + partials_merge_tol(ref, tol, 1e-5), what + ": rs against the row")
+
+
+# ---- sum-of-squares and GroupNorm partials (pq::run GNS)
+def _row16_sum(t):
+    """row16_sum over dim -2 (16 lanes): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror."""
+    k = torch.arange(16)
+    for perm in (k ^ 1, k ^ 2, (k & 8) | (7 - (k & 7)), 15 - k):
+        t = t + t[..., perm, :]
+    return t[..., 0, :]
+
+
+def _emulate_block_stats(y, form, src=None, shift=0, extra=0):
+    """The GNS epilogues on the stored y [M, N] (M % 64 == 0): a wave holds rows 16 i + fr of its 64 in NI = 4
+    registers per column. form 'sumsq' [M / 64, N]; 'gn' (mean, M2) [M / 64, N, 2] in two passes. Faults: src (the
+    statistics of other values than the stored ones), shift (every block but the last reads its rows shift rows
+    later), extra (every block but the last also adds the next block's first rows)."""
+    M, N = y.shape
+    v = (y if src is None else src).float()
+    rows = torch.arange(M).reshape(M // 64, 64)
+    rows[:-1] += shift
+    u = v[rows].reshape(M // 64, 4, 16, N)
+    if form == "sumsq":
+        q = torch.zeros(M // 64, 16, N)
+        for i in range(4):
+            q = q + u[:, i] * u[:, i]
+        out = _row16_sum(q)
+        if extra:
+            out[:-1] += (v[rows[1:, :extra]] ** 2).sum(1)
+        return out
+    mu = u[:, 0]
+    for i in range(1, 4):
+        mu = mu + u[:, i]
+    mu = _row16_sum(mu) * (1.0 / 64.0)
+    if extra:
+        mu[:-1] += v[rows[1:, :extra]].sum(1) / 64.0
+    q = torch.zeros(M // 64, 16, N)
+    for i in range(4):
+        dx = u[:, i] - mu[:, None]
+        q = q + dx * dx
+    return torch.stack([mu, _row16_sum(q)], -1)
+
+
+@pytest.mark.parametrize("form", ["sumsq", "gn"])
+def test_block_partials_emulation_and_faults(form):
+    images, hw, N, K = 5, 64, 24, 128                         # hw = 64: every block boundary is an image boundary
+    M = images * hw
+    a, w, b, _ = _gemm_inputs(M, N, K, seed=4)
+    a = (a.float() * torch.linspace(0.25, 4.0, images).repeat_interleave(hw)[:, None]).to(BF)      # images differ
+    acc = a.float() @ w.float().t() + b.float()
+    acc = _gelu_sig(acc) if form == "sumsq" else acc
+    acc[64:128, 5] = 0.0                                      # an all-zero block: exact
+    y = acc.to(BF)
+    if form == "sumsq":
+        ref, tol = sumsq_partials_bound(y, hw)
+        assert ref[1, 5].item() == 0 and tol[1, 5].item() == 0
+        view = lambda t: t
+    else:
+        ref, tol = gn_partials_bound(y.reshape(images, 8, 8, N))
+        view = lambda t: t.reshape(images, 1, N, 2)
+    assert_within(view(_emulate_block_stats(y, form)), ref, tol, f"emulated {form} partials")
+    for name, kw in [("a block read across the image boundary", dict(shift=16)),
+                     ("rows of the next block included", dict(extra=16)),
+                     ("statistics of the unrounded fp32 values", dict(src=acc))]:
+        _rejected(view(_emulate_block_stats(y, form, **kw)), ref, tol, f"{form} partials: {name}")
