@@ -128,6 +128,12 @@ KERNEL_SIGNATURES = {
     "cgs_fused_bias_act": [_P, _P, _P, _L, _I, _L, _F, _F, _I, _P],   # x, bias, y, n, C, inner, slope, scale
     "cgs_upfirdn2d": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "cgs_resize": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],        # x, y, NC, H, W, Ho, Wo, mode, align
+    # K25 Lanczos on 8-bit RGB as PIL computes it. h: x(f32), strides (n, c, h, w), out, out_f32, N, H, W, Wo, bounds,
+    # coef, ksize, tile, cap / v: in, in_f32, strides, out(f32 NHWC), N, H, Wo, Ho, bounds, coef, ksize
+    "cgs_lanczos_u8_h": [_P, _L, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P],
+    "cgs_lanczos_u8_v": [_P, _I, _L, _L, _L, _L, _P, _I, _I, _I, _I, _P, _P, _I, _P],
+    # K25 one axis of bislerp: x, y, N, C, Ho, Wo, x strides (n, c, h, w), axis, l_in, c1, c2, ratio, dtype in, out
+    "cgs_bislerp": [_P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _I, _I, _P, _P, _P, _I, _I, _P],
     "cgs_vq_nearest": [_P, _P, _P, _P, _I, _I, _I, _I, _P],            # z, codebook, idx(i64), q, M, n, D
     "cgs_grn_nhwc": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],          # x, gamma, beta, y, ws, N, HW, C
     # GRN statistics only (gx / block sums in the v2 ws layout): x, ws, N, HW, C, pre_gelu, dtype

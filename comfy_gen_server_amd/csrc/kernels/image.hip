@@ -1243,3 +1243,220 @@ CGS_EXPORT int cgs_bgemm_f32(const void* A, const void* B, float* C, int batch, 
 #undef CGS_BG
   return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------- K25b: Lanczos on 8-bit RGB
+// PIL's resize(..., LANCZOS) for 3-channel 8-bit images, bit for bit: fp32 [0, 1] pixels are quantised
+// as (uint8) clamp(255 * x, 0, 255) (one fp32 multiply, truncation), each axis is a separable pass of
+// integer taps ki = round(k * 2^22) built on the host in double precision, accumulated in int32 from
+// 1 << 21, shifted down by 22 and clipped to a byte. The horizontal pass runs first into a uint8
+// [N, H, Wo, 3] intermediate and the vertical pass reads it: order and intermediate are part of PIL's
+// result. The last pass writes (float) u8 / 255 (a true division) as NHWC fp32. An axis whose size does
+// not change has no pass, so either kernel can be the first (fp32 through strides) and the last one.
+// Tables: bounds [n_out, 2] = (first input index, tap count), coef [ksize, n_out] zero padded.
+namespace {
+constexpr int kLanczosBits = 22;
+constexpr int kLanczosLds = 48 * 1024;
+
+__device__ __forceinline__ int lanczos_quant(float v) {
+  return (int)fminf(fmaxf(__fmul_rn(255.0f, v), 0.0f), 255.0f);
+}
+
+__device__ __forceinline__ int lanczos_clip(int acc) { return min(max(acc >> kLanczosBits, 0), 255); }
+
+// One workgroup per (image row, tile of `tile` output pixels): the input span of the tile is quantised
+// into LDS once as bytes, then one lane per output pixel runs its taps over the three channels.
+template <bool OUTF>
+__global__ void __launch_bounds__(256) lanczos_h_kernel(const float* __restrict__ x, long long sn, long long sc,
+                                                        long long sh, long long sw, void* __restrict__ out, int H,
+                                                        int W, int Wo, const int* __restrict__ bounds,
+                                                        const int* __restrict__ coef, int ksize, int tile, int cap,
+                                                        int ntiles) {
+  extern __shared__ uint8_t lz_row[];
+  const int x0 = (int)(blockIdx.x % (unsigned)ntiles) * tile, x1 = min(x0 + tile, Wo);
+  const long long rowid = blockIdx.x / (unsigned)ntiles;   // n * H + y
+  const int s0 = max(bounds[2 * x0], 0);
+  const int s1 = min(bounds[2 * (x1 - 1)] + bounds[2 * (x1 - 1) + 1], W);
+  const int span = s1 - s0;
+  if (span <= 0 || span > cap) return;   // tables that do not belong to this launch: write nothing
+  const float* src = x + (rowid / H) * sn + (rowid % H) * sh;
+  for (int e = threadIdx.x; e < span * 3; e += 256) {
+    const int p = e / 3, c = e - 3 * p;
+    lz_row[e] = (uint8_t)lanczos_quant(src[(s0 + p) * sw + c * sc]);
+  }
+  __syncthreads();
+  for (int xx = x0 + threadIdx.x; xx < x1; xx += 256) {
+    const int xmin = bounds[2 * xx], cnt = bounds[2 * xx + 1];
+    if (xmin < s0 || cnt > ksize || xmin + cnt > s1) continue;
+    const uint8_t* p = lz_row + (xmin - s0) * 3;
+    int a0 = 1 << (kLanczosBits - 1), a1 = a0, a2 = a0;
+    for (int j = 0; j < cnt; ++j) {
+      const int k = coef[(long long)j * Wo + xx];
+      a0 += (int)p[3 * j] * k;
+      a1 += (int)p[3 * j + 1] * k;
+      a2 += (int)p[3 * j + 2] * k;
+    }
+    const long long o = (rowid * Wo + xx) * 3;
+    if constexpr (OUTF) {
+      float* y = reinterpret_cast<float*>(out) + o;
+      y[0] = __fdiv_rn((float)lanczos_clip(a0), 255.0f);
+      y[1] = __fdiv_rn((float)lanczos_clip(a1), 255.0f);
+      y[2] = __fdiv_rn((float)lanczos_clip(a2), 255.0f);
+    } else {
+      uint8_t* y = reinterpret_cast<uint8_t*>(out) + o;
+      y[0] = (uint8_t)lanczos_clip(a0);
+      y[1] = (uint8_t)lanczos_clip(a1);
+      y[2] = (uint8_t)lanczos_clip(a2);
+    }
+  }
+}
+
+// One lane per output byte column (x * 3 + c) of one output row: every tap reads a coalesced run of
+// the uint8 rows (INF: the fp32 input through its strides, quantised on the way); taps are wave-uniform.
+template <bool INF>
+__global__ void __launch_bounds__(256) lanczos_v_kernel(const void* __restrict__ in, long long sn, long long sc,
+                                                        long long sh, long long sw, float* __restrict__ out, int H,
+                                                        int Wo, int Ho, const int* __restrict__ bounds,
+                                                        const int* __restrict__ coef, int ksize, int nseg) {
+  const int cols = Wo * 3;
+  const int col = (int)(blockIdx.x % (unsigned)nseg) * 256 + threadIdx.x;
+  const long long rowid = blockIdx.x / (unsigned)nseg;   // n * Ho + yy
+  const long long n = rowid / Ho;
+  const int yy = (int)(rowid % Ho);
+  const int ymin = bounds[2 * yy], cnt = bounds[2 * yy + 1];
+  if (col >= cols || ymin < 0 || cnt > ksize || ymin + cnt > H) return;
+  int acc = 1 << (kLanczosBits - 1);
+  if constexpr (INF) {
+    const int px = col / 3, c = col - 3 * px;
+    const float* src = reinterpret_cast<const float*>(in) + n * sn + c * sc + px * sw;
+    for (int j = 0; j < cnt; ++j) acc += lanczos_quant(src[(ymin + j) * sh]) * coef[(long long)j * Ho + yy];
+  } else {
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(in) + (n * H + ymin) * cols + col;
+    for (int j = 0; j < cnt; ++j) acc += (int)src[(long long)j * cols] * coef[(long long)j * Ho + yy];
+  }
+  out[rowid * cols + col] = __fdiv_rn((float)lanczos_clip(acc), 255.0f);
+}
+}  // namespace
+
+// Horizontal pass: x fp32 [N, 3, H, W] by element strides -> out [N, H, Wo, 3], uint8 (out_f32 = 0, the
+// vertical pass follows) or fp32 / 255 (out_f32 = 1, the height does not change). tile = output pixels per
+// workgroup, cap = the longest input span (pixels) of one tile: cap * 3 bytes of LDS.
+CGS_EXPORT int cgs_lanczos_u8_h(const float* x, long long sn, long long sc, long long sh, long long sw, void* out,
+                                int out_f32, int N, int H, int W, int Wo, const int* bounds, const int* coef,
+                                int ksize, int tile, int cap, hipStream_t stream) {
+  if (N <= 0 || H <= 0 || Wo <= 0) return 0;
+  if (W <= 0 || ksize <= 0 || tile <= 0 || cap <= 0 || cap > W || (long long)cap * 3 > kLanczosLds)
+    return (int)hipErrorInvalidValue;
+  const int ntiles = (Wo + tile - 1) / tile;
+  const long long blocks = (long long)N * H * ntiles;
+  if (blocks > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  const size_t lds = (size_t)cap * 3;
+  if (out_f32)
+    lanczos_h_kernel<true><<<(unsigned)blocks, 256, lds, stream>>>(x, sn, sc, sh, sw, out, H, W, Wo, bounds, coef,
+                                                                   ksize, tile, cap, ntiles);
+  else
+    lanczos_h_kernel<false><<<(unsigned)blocks, 256, lds, stream>>>(x, sn, sc, sh, sw, out, H, W, Wo, bounds, coef,
+                                                                    ksize, tile, cap, ntiles);
+  return (int)hipGetLastError();
+}
+
+// Vertical pass -> out fp32 [N, Ho, Wo, 3]. in_f32 = 0: in is the uint8 [N, H, Wo, 3] of the horizontal
+// pass (strides unused); in_f32 = 1: in is the fp32 input by element strides (the width does not change).
+CGS_EXPORT int cgs_lanczos_u8_v(const void* in, int in_f32, long long sn, long long sc, long long sh, long long sw,
+                                float* out, int N, int H, int Wo, int Ho, const int* bounds, const int* coef,
+                                int ksize, hipStream_t stream) {
+  if (N <= 0 || Ho <= 0 || Wo <= 0) return 0;
+  if (H <= 0 || ksize <= 0 || Wo > 0x7fffffff / 3) return (int)hipErrorInvalidValue;
+  const int nseg = (Wo * 3 + 255) / 256;
+  const long long blocks = (long long)N * Ho * nseg;
+  if (blocks > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  if (in_f32)
+    lanczos_v_kernel<true><<<(unsigned)blocks, 256, 0, stream>>>(in, sn, sc, sh, sw, out, H, Wo, Ho, bounds, coef,
+                                                                 ksize, nseg);
+  else
+    lanczos_v_kernel<false><<<(unsigned)blocks, 256, 0, stream>>>(in, sn, sc, sh, sw, out, H, Wo, Ho, bounds, coef,
+                                                                  ksize, nseg);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- K25c: bislerp (latent resize)
+// One axis of the spherical-linear resize of utils.image.bislerp: out[.., t] = slerp(x[.., c1[t]],
+// x[.., c2[t]], r[t]) over the channel vectors, with the reference's own (c1, c2, r) tables. One lane per
+// output pixel: norms, then the dot of the normalised vectors, then the C outputs. The reference's two
+// overwrites (nearly parallel -> b1, nearly antiparallel -> lerp) are taken as branches. x by element
+// strides (any _DT), y contiguous [N, C, Ho, Wo]; fp32 math.
+namespace {
+template <int DTI, int DTO>
+__global__ void __launch_bounds__(256) bislerp_kernel(const void* __restrict__ x, void* __restrict__ y, int N, int C,
+                                                      int Ho, int Wo, long long sn, long long sc, long long sh,
+                                                      long long sw, int axis, int lin, const int* __restrict__ c1,
+                                                      const int* __restrict__ c2, const float* __restrict__ rt) {
+  // no FMA contraction: the compiler keeps a second copy of the channel loops for unit channel stride and
+  // contracts the two differently, and the result must not depend on the layout of x
+#pragma clang fp contract(off)
+  const long long plane = (long long)Ho * Wo, total = (long long)N * plane;
+  const float hi = (float)(1.0 - 1e-5), lo = (float)(1e-5 - 1.0);
+  for (long long o = blockIdx.x * 256LL + threadIdx.x; o < total; o += (long long)gridDim.x * 256) {
+    const int ox = (int)(o % Wo), oy = (int)((o / Wo) % Ho);
+    const long long n = o / plane;
+    const int t = axis ? oy : ox;
+    const int i1 = min(max(c1[t], 0), lin - 1), i2 = min(max(c2[t], 0), lin - 1);
+    const float r = rt[t], q = 1.0f - r;
+    const long long st = axis ? sh : sw;
+    const long long base = n * sn + (axis ? ox * sw : oy * sh);
+    const long long p1 = base + i1 * st, p2 = base + i2 * st;
+    float ss1 = 0.f, ss2 = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float a = ldv<DTI>(x, p1 + c * sc), b = ldv<DTI>(x, p2 + c * sc);
+      ss1 += a * a;
+      ss2 += b * b;
+    }
+    const float n1 = sqrtf(ss1), n2 = sqrtf(ss2);
+    float dot = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float a = ldv<DTI>(x, p1 + c * sc), b = ldv<DTI>(x, p2 + c * sc);
+      dot += (n1 == 0.f ? 0.f : a / n1) * (n2 == 0.f ? 0.f : b / n2);
+    }
+    const long long yo = n * C * plane + (long long)oy * Wo + ox;
+    if (dot > hi) {
+      for (int c = 0; c < C; ++c) stv<DTO>(y, yo + c * plane, ldv<DTI>(x, p1 + c * sc));
+    } else if (dot < lo) {
+      for (int c = 0; c < C; ++c)
+        stv<DTO>(y, yo + c * plane, ldv<DTI>(x, p1 + c * sc) * q + ldv<DTI>(x, p2 + c * sc) * r);
+    } else {
+      const float omega = acosf(dot), so = sinf(omega);
+      const float w1 = sinf(q * omega) / so, w2 = sinf(r * omega) / so;
+      const float mag = n1 * q + n2 * r;
+      for (int c = 0; c < C; ++c) {
+        const float a = ldv<DTI>(x, p1 + c * sc), b = ldv<DTI>(x, p2 + c * sc);
+        stv<DTO>(y, yo + c * plane, (w1 * (n1 == 0.f ? 0.f : a / n1) + w2 * (n2 == 0.f ? 0.f : b / n2)) * mag);
+      }
+    }
+  }
+}
+}  // namespace
+
+// axis 0: resize W (tables of Wo entries, lin = W); axis 1: resize H (tables of Ho entries, lin = H).
+// The other extent of y equals x's. dti / dto: CgsDType of x / y.
+CGS_EXPORT int cgs_bislerp(const void* x, void* y, int N, int C, int Ho, int Wo, long long sn, long long sc,
+                           long long sh, long long sw, int axis, int lin, const int* c1, const int* c2,
+                           const float* r, int dti, int dto, hipStream_t stream) {
+  const long long total = (long long)N * Ho * Wo;
+  if (total <= 0 || C <= 0) return 0;
+  if (lin <= 0 || (axis != 0 && axis != 1)) return (int)hipErrorInvalidValue;
+#define CGS_BSL(TI, TO)                                                                                           \
+  bislerp_kernel<TI, TO><<<grid_for(total), 256, 0, stream>>>(x, y, N, C, Ho, Wo, sn, sc, sh, sw, axis, lin, c1, c2, r)
+  if (dto == CGS_F32) {
+    if (dti == CGS_F32) CGS_BSL(CGS_F32, CGS_F32);
+    else if (dti == CGS_BF16) CGS_BSL(CGS_BF16, CGS_F32);
+    else if (dti == CGS_F16) CGS_BSL(CGS_F16, CGS_F32);
+    else return (int)hipErrorInvalidValue;
+  } else if (dti == CGS_F32) {
+    if (dto == CGS_BF16) CGS_BSL(CGS_F32, CGS_BF16);
+    else if (dto == CGS_F16) CGS_BSL(CGS_F32, CGS_F16);
+    else return (int)hipErrorInvalidValue;
+  } else {
+    return (int)hipErrorInvalidValue;
+  }
+#undef CGS_BSL
+  return (int)hipGetLastError();
+}

@@ -24,5 +24,5 @@ from .core import (  # noqa: F401
     attention_with_probs, philox_randn, euler_ancestral_philox, brownian_increment, step_param, sampler_step_dev,
     step_advance, vae_out_u8, region_accumulate, region_normalize, clip_embed, pooled_gather,
     layernorm_stats, layernorm_stats_for, lnfold_weights, linear_lnfold, lnfold_available, fourier_filter, tome_match,
-    rng_key_scope,
+    rng_key_scope, lanczos_resize, lanczos_reference, lanczos_tables, bislerp, bislerp_tables,
 )

@@ -8,9 +8,11 @@ Tensor conventions
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -1518,6 +1520,240 @@ def interpolate(x: torch.Tensor, size, mode: str = "nearest", align_corners: boo
         return y
     kw = {"align_corners": align_corners} if mode in ("bilinear", "bicubic") else {}
     return F.interpolate(x, size=(Ho, Wo), mode=mode, **kw)
+
+
+# Lanczos (PIL's 8-bit integer algorithm) and bislerp: the two common_upscale methods beside cgs_resize (K25)
+_LANCZOS_BITS = 22
+_LANCZOS_TILE = 256        # output pixels per workgroup of the horizontal pass
+_LANCZOS_LDS_PIXELS = 16384   # 48 KiB of LDS holds this many quantised RGB pixels
+_LANCZOS_CACHE_MAX = 16
+_lanczos_dev: "collections.OrderedDict" = collections.OrderedDict()
+_bislerp_dev: dict = {}
+
+
+def _lanczos_filter(x: float) -> float:
+    def sinc(v):
+        if v == 0.0:
+            return 1.0
+        v = v * math.pi
+        return math.sin(v) / v
+    return sinc(x) * sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+def lanczos_tables(n_in: int, n_out: int):
+    """Integer taps of one axis of PIL's ``resize(..., LANCZOS)`` on 8-bit images, built in double precision
+    on the host: ``bounds`` int32 ``[n_out, 2]`` (first input index, tap count) and ``coef`` int32
+    ``[n_out, ksize]``, zero past the count. Output ``i`` is
+    ``clip(((1 << 21) + sum_j pix[bounds[i, 0] + j] * coef[i, j]) >> 22, 0, 255)``."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 3.0 * fs
+    ss = 1.0 / fs
+    rows, bounds = [], np.empty((n_out, 2), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n_in)
+        k = [_lanczos_filter((j + xmin - center + 0.5) * ss) for j in range(xmax - xmin)]
+        ww = 0.0
+        for v in k:   # PIL's own left-to-right double sum: the rounding of ww decides the last bit of a tap
+            ww += v
+        if ww != 0.0:
+            k = [v / ww for v in k]
+        rows.append([int(v * (1 << _LANCZOS_BITS) + (0.5 if v >= 0 else -0.5)) for v in k])
+        bounds[xx] = (xmin, xmax - xmin)
+    coef = np.zeros((n_out, max(len(r) for r in rows)), dtype=np.int32)
+    for xx, r in enumerate(rows):
+        coef[xx, :len(r)] = r
+    return bounds, coef
+
+
+def _lanczos_identity(n: int):
+    """Tables of an axis that is not resized: one tap of weight 1, so a pass with them only quantises."""
+    bounds = np.stack([np.arange(n, dtype=np.int32), np.ones(n, dtype=np.int32)], axis=1)
+    return bounds, np.full((n, 1), 1 << _LANCZOS_BITS, dtype=np.int32)
+
+
+def _lanczos_quantise(x: torch.Tensor) -> np.ndarray:
+    """fp32 ``[N, 3, H, W]`` -> uint8 ``[N, H, W, 3]`` as the PIL path does: one fp32 multiply, clamp, truncate."""
+    a = x.detach().to("cpu", torch.float32).movedim(1, -1).numpy()
+    return np.clip(np.float32(255.0) * a, 0, 255).astype(np.uint8)
+
+
+def _lanczos_pass(img: np.ndarray, axis: int, n_out: int) -> np.ndarray:
+    bounds, coef = lanczos_tables(img.shape[axis], n_out)
+    src = np.moveaxis(img, axis, 0).astype(np.int32)
+    out = np.empty((n_out,) + src.shape[1:], dtype=np.uint8)
+    for i in range(n_out):
+        x0, n = int(bounds[i, 0]), int(bounds[i, 1])
+        acc = np.tensordot(coef[i, :n], src[x0:x0 + n], axes=(0, 0)) + (1 << (_LANCZOS_BITS - 1))
+        out[i] = np.clip(acc >> _LANCZOS_BITS, 0, 255)
+    return np.moveaxis(out, 0, axis)
+
+
+def lanczos_reference(x: torch.Tensor, width: int, height: int) -> torch.Tensor:
+    """The integer Lanczos algorithm of ``lanczos_resize`` in numpy on the CPU (no PIL): quantise, horizontal
+    pass into uint8, vertical pass on that, ``u8 / 255``. An axis whose size does not change has no pass."""
+    img = _lanczos_quantise(x)
+    if img.shape[2] != width:
+        img = _lanczos_pass(img, 2, width)
+    if img.shape[1] != height:
+        img = _lanczos_pass(img, 1, height)
+    out = torch.from_numpy(img.astype(np.float32) / np.float32(255.0)).movedim(-1, 1)
+    return out.to(x.device, x.dtype)
+
+
+def _lanczos_pil(samples, width, height):
+    from PIL import Image
+    imgs = [Image.fromarray(np.clip(255.0 * im.movedim(0, -1).cpu().numpy(), 0, 255).astype(np.uint8)) for im in samples]
+    imgs = [im.resize((width, height), resample=Image.Resampling.LANCZOS) for im in imgs]
+    imgs = [torch.from_numpy(np.array(im).astype(np.float32) / 255.0).movedim(-1, 0) for im in imgs]
+    return torch.stack(imgs).to(samples.device, samples.dtype)
+
+
+def _lanczos_device_tables(n_in: int, n_out: int, device):
+    """(bounds, coef [ksize, n_out], ksize, tile, cap) of one axis on ``device``; a small LRU cache, since a
+    table of a 16k axis is megabytes. ``n_in == n_out`` gives the identity tables. cap is the longest input
+    span of one tile of the horizontal pass, or 0 when no tile size fits the LDS row."""
+    key = (n_in, n_out, device.index)
+    hit = _lanczos_dev.get(key)
+    if hit is not None:
+        _lanczos_dev.move_to_end(key)
+        return hit
+    bounds, coef = _lanczos_identity(n_in) if n_in == n_out else lanczos_tables(n_in, n_out)
+    end = bounds[:, 0] + bounds[:, 1]
+    tile, cap = _LANCZOS_TILE, 0
+    while tile >= 1:
+        first = np.arange(0, n_out, tile)
+        cap = int((end[np.minimum(first + tile, n_out) - 1] - bounds[first, 0]).max())
+        if cap <= _LANCZOS_LDS_PIXELS:
+            break
+        tile, cap = tile // 2, 0
+    hit = (torch.from_numpy(bounds).to(device), torch.from_numpy(np.ascontiguousarray(coef.T)).to(device),
+           coef.shape[1], max(tile, 1), cap)
+    _lanczos_dev[key] = hit
+    while len(_lanczos_dev) > _LANCZOS_CACHE_MAX:
+        _lanczos_dev.popitem(last=False)
+    return hit
+
+
+def lanczos_resize(x: torch.Tensor, width: int, height: int) -> torch.Tensor:
+    """Lanczos resize of ``[N, C, H, W]`` images in [0, 1] as PIL computes it on 8-bit pixels (K25).
+    Device path (fp32, 3 channels): ``cgs_lanczos_u8_h`` then ``cgs_lanczos_u8_v``, bit-identical to PIL;
+    the input is read through its strides and the result is an ``[N, 3, h, w]`` view of NHWC memory.
+    Everything else (CPU, other dtypes and channel counts) is the PIL code itself."""
+    be = backend_for("resample", x, "cgs_lanczos_u8_h")
+    if (be == "hip" and x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] == 3 and x.numel() > 0
+            and width > 0 and height > 0):
+        N, _, H, W = x.shape
+        ht = _lanczos_device_tables(W, width, x.device) if W != width else None
+        if ht is None or ht[4] > 0:   # a horizontal window longer than the LDS row (W > 16384 only) stays on PIL
+            count("resample", "hip")
+            sn, sc, sh, sw = x.stride()
+            y = torch.empty((N, height, width, 3), device=x.device, dtype=torch.float32)
+            if ht is not None:
+                hb, hc, hk, tile, cap = ht
+                last = H == height
+                tmp = y if last else torch.empty((N, H, width, 3), device=x.device, dtype=torch.uint8)
+                _check(_lib().cgs_lanczos_u8_h(x.data_ptr(), sn, sc, sh, sw, tmp.data_ptr(), int(last), N, H, W,
+                                               width, hb.data_ptr(), hc.data_ptr(), hk, tile, cap, _stream()),
+                       "cgs_lanczos_u8_h")
+                if last:
+                    return y.movedim(-1, 1)
+                src, f32 = tmp, 0
+            else:
+                src, f32 = x, 1
+            vb, vc, vk, _, _ = _lanczos_device_tables(H, height, x.device)
+            _check(_lib().cgs_lanczos_u8_v(src.data_ptr(), f32, sn, sc, sh, sw, y.data_ptr(), N, H, width, height,
+                                           vb.data_ptr(), vc.data_ptr(), vk, _stream()), "cgs_lanczos_u8_v")
+            return y.movedim(-1, 1)
+    count("resample", "torch")
+    return _lanczos_pil(x, width, height)
+
+
+def bislerp_tables(n_in: int, n_out: int):
+    """``(c1, c2, ratio)`` of one axis of bislerp: the reference's own fp32 ``coords`` expression, so the
+    device lookups equal the reference's."""
+    ramp = torch.arange(n_out, dtype=torch.float32) * (n_in / n_out)
+    c1 = ramp.floor().long()
+    ratios = ramp - c1
+    c2 = (c1 + 1).clamp(max=n_in - 1)
+    return c1, c2, ratios
+
+
+def _bislerp_device_tables(n_in: int, n_out: int, device):
+    # never evicted: a captured sampler graph keeps the addresses of the tables its eager first run made
+    key = (n_in, n_out, device.index)
+    hit = _bislerp_dev.get(key)
+    if hit is None:
+        c1, c2, r = bislerp_tables(n_in, n_out)
+        hit = _bislerp_dev[key] = (c1.to(torch.int32).to(device), c2.to(torch.int32).to(device), r.to(device))
+    return hit
+
+
+def _bislerp_torch(samples, width, height):
+    def slerp(b1, b2, r):
+        c = b1.shape[-1]
+        n1 = torch.norm(b1, dim=-1, keepdim=True)
+        n2 = torch.norm(b2, dim=-1, keepdim=True)
+        b1n = b1 / n1
+        b2n = b2 / n2
+        b1n[n1.expand(-1, c) == 0.0] = 0.0
+        b2n[n2.expand(-1, c) == 0.0] = 0.0
+        dot = (b1n * b2n).sum(1)
+        omega = torch.acos(dot)
+        so = torch.sin(omega)
+        res = (torch.sin((1.0 - r.squeeze(1)) * omega) / so).unsqueeze(1) * b1n + \
+              (torch.sin(r.squeeze(1) * omega) / so).unsqueeze(1) * b2n
+        res *= (n1 * (1.0 - r) + n2 * r).expand(-1, c)
+        res[dot > 1 - 1e-5] = b1[dot > 1 - 1e-5]
+        res[dot < 1e-5 - 1] = (b1 * (1.0 - r) + b2 * r)[dot < 1e-5 - 1]
+        return res
+
+    orig_dtype = samples.dtype
+    samples = samples.float()
+    n, c, h, w = samples.shape
+    h_new, w_new = height, width
+    c1, c2, r = bislerp_tables(w, w_new)
+    c1 = c1.view(1, 1, 1, -1).expand((n, c, h, w_new)).to(samples.device)
+    c2 = c2.view(1, 1, 1, -1).expand((n, c, h, w_new)).to(samples.device)
+    r = r.view(1, 1, 1, -1).expand((n, 1, h, w_new)).to(samples.device)
+    p1 = samples.gather(-1, c1).movedim(1, -1).reshape((-1, c))
+    p2 = samples.gather(-1, c2).movedim(1, -1).reshape((-1, c))
+    r = r.movedim(1, -1).reshape((-1, 1))
+    result = slerp(p1, p2, r).reshape(n, h, w_new, c).movedim(-1, 1)
+    c1, c2, r = bislerp_tables(h, h_new)
+    c1 = c1.view(1, 1, -1, 1).expand((n, c, h_new, w_new)).to(samples.device)
+    c2 = c2.view(1, 1, -1, 1).expand((n, c, h_new, w_new)).to(samples.device)
+    r = r.view(1, 1, -1, 1).expand((n, 1, h_new, w_new)).to(samples.device)
+    p1 = result.gather(-2, c1).movedim(1, -1).reshape((-1, c))
+    p2 = result.gather(-2, c2).movedim(1, -1).reshape((-1, c))
+    r = r.movedim(1, -1).reshape((-1, 1))
+    result = slerp(p1, p2, r).reshape(n, h_new, w_new, c).movedim(-1, 1)
+    return result.to(orig_dtype)
+
+
+def bislerp(x: torch.Tensor, width: int, height: int) -> torch.Tensor:
+    """Spherical-linear bilinear resize of ``[N, C, H, W]`` latents (channel vectors slerped): W, then H on
+    the fp32 intermediate. Device path: two ``cgs_bislerp`` launches, input read through its strides."""
+    be = backend_for("resample", x, "cgs_bislerp")
+    if be == "hip" and x.dim() == 4 and x.dtype in _DT and x.numel() > 0 and width > 0 and height > 0:
+        count("resample", "hip")
+        N, C, H, W = x.shape
+        sn, sc, sh, sw = x.stride()
+        c1, c2, r = _bislerp_device_tables(W, width, x.device)
+        mid = torch.empty((N, C, H, width), device=x.device, dtype=torch.float32)
+        _check(_lib().cgs_bislerp(x.data_ptr(), mid.data_ptr(), N, C, H, width, sn, sc, sh, sw, 0, W,
+                                  c1.data_ptr(), c2.data_ptr(), r.data_ptr(), _DT[x.dtype], 0, _stream()),
+               "cgs_bislerp")
+        c1, c2, r = _bislerp_device_tables(H, height, x.device)
+        y = torch.empty((N, C, height, width), device=x.device, dtype=x.dtype)
+        _check(_lib().cgs_bislerp(mid.data_ptr(), y.data_ptr(), N, C, height, width, C * H * width, H * width,
+                                  width, 1, 1, H, c1.data_ptr(), c2.data_ptr(), r.data_ptr(), 0, _DT[x.dtype],
+                                  _stream()), "cgs_bislerp")
+        return y
+    count("resample", "torch")
+    return _bislerp_torch(x, width, height)
 
 
 def clip_embed(ids: torch.Tensor, tok_weight: torch.Tensor, pos_weight: torch.Tensor) -> torch.Tensor:

@@ -1,7 +1,7 @@
 """Image / latent resizing and tiling utilities (parity: ``comfy/utils.py:318-454``; K24/K25).
 
-common_upscale: nearest-exact / bilinear / area / bicubic / lanczos (PIL) / bislerp, optional
-center crop. tiled_scale: feather-blended tiled application of a function (VAE / upscalers).
+common_upscale: nearest-exact / bilinear / area / bicubic / lanczos (PIL's 8-bit algorithm) / bislerp,
+optional center crop; every method is an op with a HIP kernel on the device. tiled_scale: feather-blended tiled application of a function (VAE / upscalers).
 """
 from __future__ import annotations
 
@@ -15,60 +15,14 @@ import torch.nn.functional as F
 
 def bislerp(samples, width, height):
     """Spherical-linear bilinear resize of latents (channel vectors slerped)."""
-    def slerp(b1, b2, r):
-        c = b1.shape[-1]
-        n1 = torch.norm(b1, dim=-1, keepdim=True)
-        n2 = torch.norm(b2, dim=-1, keepdim=True)
-        b1n = b1 / n1
-        b2n = b2 / n2
-        b1n[n1.expand(-1, c) == 0.0] = 0.0
-        b2n[n2.expand(-1, c) == 0.0] = 0.0
-        dot = (b1n * b2n).sum(1)
-        omega = torch.acos(dot)
-        so = torch.sin(omega)
-        res = (torch.sin((1.0 - r.squeeze(1)) * omega) / so).unsqueeze(1) * b1n + \
-              (torch.sin(r.squeeze(1) * omega) / so).unsqueeze(1) * b2n
-        res *= (n1 * (1.0 - r) + n2 * r).expand(-1, c)
-        res[dot > 1 - 1e-5] = b1[dot > 1 - 1e-5]
-        res[dot < 1e-5 - 1] = (b1 * (1.0 - r) + b2 * r)[dot < 1e-5 - 1]
-        return res
-
-    def coords(l_in, l_out):
-        ramp = torch.arange(l_out, dtype=torch.float32) * (l_in / l_out)
-        c1 = ramp.floor().long()
-        ratios = ramp - c1
-        c2 = (c1 + 1).clamp(max=l_in - 1)
-        return c1, c2, ratios
-
-    orig_dtype = samples.dtype
-    samples = samples.float()
-    n, c, h, w = samples.shape
-    h_new, w_new = height, width
-    c1, c2, r = coords(w, w_new)
-    c1 = c1.view(1, 1, 1, -1).expand((n, c, h, w_new)).to(samples.device)
-    c2 = c2.view(1, 1, 1, -1).expand((n, c, h, w_new)).to(samples.device)
-    r = r.view(1, 1, 1, -1).expand((n, 1, h, w_new)).to(samples.device)
-    p1 = samples.gather(-1, c1).movedim(1, -1).reshape((-1, c))
-    p2 = samples.gather(-1, c2).movedim(1, -1).reshape((-1, c))
-    r = r.movedim(1, -1).reshape((-1, 1))
-    result = slerp(p1, p2, r).reshape(n, h, w_new, c).movedim(-1, 1)
-    c1, c2, r = coords(h, h_new)
-    c1 = c1.view(1, 1, -1, 1).expand((n, c, h_new, w_new)).to(samples.device)
-    c2 = c2.view(1, 1, -1, 1).expand((n, c, h_new, w_new)).to(samples.device)
-    r = r.view(1, 1, -1, 1).expand((n, 1, h_new, w_new)).to(samples.device)
-    p1 = result.gather(-2, c1).movedim(1, -1).reshape((-1, c))
-    p2 = result.gather(-2, c2).movedim(1, -1).reshape((-1, c))
-    r = r.movedim(1, -1).reshape((-1, 1))
-    result = slerp(p1, p2, r).reshape(n, h_new, w_new, c).movedim(-1, 1)
-    return result.to(orig_dtype)
+    from .. import ops
+    return ops.bislerp(samples, width, height)
 
 
 def lanczos(samples, width, height):
-    from PIL import Image
-    imgs = [Image.fromarray(np.clip(255.0 * im.movedim(0, -1).cpu().numpy(), 0, 255).astype(np.uint8)) for im in samples]
-    imgs = [im.resize((width, height), resample=Image.Resampling.LANCZOS) for im in imgs]
-    imgs = [torch.from_numpy(np.array(im).astype(np.float32) / 255.0).movedim(-1, 0) for im in imgs]
-    return torch.stack(imgs).to(samples.device, samples.dtype)
+    """PIL's 8-bit Lanczos resize: HIP kernels for fp32 RGB on the device, PIL itself elsewhere."""
+    from .. import ops
+    return ops.lanczos_resize(samples, width, height)
 
 
 def common_upscale(samples, width, height, upscale_method, crop):
