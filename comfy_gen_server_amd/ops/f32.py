@@ -42,6 +42,13 @@ def _vec_ok(t: torch.Tensor) -> bool:
     return t.data_ptr() % 16 == 0
 
 
+def _vec(t: torch.Tensor) -> torch.Tensor:
+    """t as contiguous rows on a 16-byte-aligned base. ``contiguous()`` returns a dense view as it is, whatever its
+    base (a slice of a flat buffer that starts at an odd element): that one is copied."""
+    t = t.contiguous()
+    return t if _vec_ok(t) else t.clone()
+
+
 def available(name: str = "cgs_gemm_f32") -> bool:
     return _native.has_kernel(name)
 
@@ -75,13 +82,13 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias, residual, act, out):
         return None
     a = x.reshape(-1, K)
     if a.stride(-1) != 1 or (a.shape[0] > 1 and a.stride(0) < K) or a.stride(0) % 4 or not _vec_ok(a):
-        a = a.contiguous()
+        a = _vec(a)
     if K % 4:         # row strides must be float4-aligned: pad K (the kernel zero-fills the K tail)
         Kp = (K + 3) // 4 * 4
         a = torch.nn.functional.pad(a, (0, Kp - K))
         weight = torch.nn.functional.pad(weight, (0, Kp - K))
     M = a.shape[0]
-    w = weight if weight.is_contiguous() and _vec_ok(weight) else weight.contiguous()
+    w = _vec(weight)
     b = _f32(bias, x.device)
     r = None
     if residual is not None:

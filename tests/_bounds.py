@@ -1,6 +1,7 @@
 """Per-element worst-case error bounds of the bf16 GEMM, conv and attention kernels (test_kernel_bounds_*.py) and
 of the bf16 / fp16 GroupNorm, LayerNorm, depthwise-conv and softmax2 kernels (test_norm_bounds_gpu.py), of the GRN
-family and of the planar image-space kernels (test_image_bounds_gpu.py).
+family and of the planar image-space kernels (test_image_bounds_gpu.py), and of the fp32 GEMM, conv, norm and
+attention kernels (test_f32_bounds_gpu.py).
 
 Every ``*_bound`` function takes the operands the kernel is given (CPU or GPU tensors of any float type), builds
 the result in fp64 and returns ``(ref, tol)``: two fp64 tensors of the output's shape. ``assert_within`` then
@@ -151,6 +152,38 @@ row16_sum (4): L = 8; positive terms only, tol = C_ACC (L + 1) e ref (+ 1: the s
 GroupNorm partials (pq::run GNS == 1), [N, HW / 64, C, 2], two passes over the wave's registers: the sum of 4 values in
 sequence (3) and row16_sum (4), L = 7, the product by 1 / 64 is exact; the structure is _ln_stats's:
   dmean = C_ACC L e mean |v| + e |mean|;  dM2 = C_ACC (L + 4) e M2 + 64 dmean^2    (v - m, its square, 8 additions)
+
+The fp32 kernels (csrc/kernels/f32.hip, ops/f32.py; test_f32_bounds_*.py): u(float32) = e everywhere, _store_dt for
+the norms. Nothing is rounded to a storage type, so every term is a rounding of the code.
+GEMM / conv (f32_gemm_kernel, ``dtype=torch.float32`` on gemm_bound, gemm_act_bound, conv_bound, conv_act_bound; the
+default dtype leaves every bf16 caller's (ref, tol) as it was, bit for bit). The epilogue is
+  v = fmaf(acc, alpha, bias)  one rounding;  v = act(v);  v += R  one rounding;  the store does not round.
+  tol = e |ref| (1 + 2e) + [R] e |pre| + C_ACC K e mag: the first term is the last rounding (the fma, or the addition
+  of R), the second the fma when R follows it, the third the MFMA accumulation (exact fp32 products, one rounding
+  a k step, in the permuted k order of the 16-deep slices). alpha is the fp32 value the kernel is passed.
+  With an activation d_pre = C_ACC K e mag + e |pre| (the fma before it) and
+  tol = e |ref| (1 + 2e) + ([R] e |act(pre)| + slope_act d_pre + act_err) (1 + e).
+  A bare GELU, or code CGS_ACT_GELU, is gelu_f here, 0.5f x (1.0f + erff(x 0.70710678f)), not gelu_sig (GELU_ABS does
+  not apply): t = fl(x c) with c within e of 1 / sqrt 2 is off by 2 e |t|, times erf' = 2 / sqrt(pi) exp(-t^2); erff
+  adds ERFF_REL |erf t|; 1 + erf rounds once, e (1 + erf t); 0.5 x is exact and the last product rounds once more.
+  The error of 1 + erf is absolute, not relative to the result -- it cancels for x << 0 -- so
+    act_err = 0.5 |x| (4 / sqrt(pi) e |t| exp(-t^2) + ERFF_REL |erf t| + e (1 + erf t)) + 2 e |gelu(x)|.
+  gelu_tanh, quick_gelu, silu and relu go through act_apply: the SIG / LIN terms above.
+GroupNorm (cgs_groupnorm_f32): gn_f32_form restates S = gn_slices(N, HW) and the P pixel lanes of a channel chunk,
+  gn_f32_depth the (Lb, L) of the three kernels; the statistics formulas are those of the bf16 kernels with E2 taken
+  over the real slices [HW s // S, HW (s + 1) // S), shift = the slice's first pixel with its pre-add. New here:
+  v = fl(x + pre_add) is rounded before use (gn_ld: one more step of R in L; e |v| |a| in the output, inside 6 e mag);
+  a = fl(gamma rstd) and b = fl(beta - fl(mean a)) are stored and the output is fmaf(v, a, b): five roundings, each
+  relative to a term of mag, inside the same 6 e mag; SiLU is o / (1.0f + expf(-o)) with a true division (_silu_div).
+LayerNorm (cgs_layernorm_f32): one wave a row, two passes, L = ln_f32_depth(C) = ceil(C / 256) + 2 + 6 through the
+  ``depth=`` of layernorm_bound; ((x - m) r) w + b is four roundings, inside 6 e (|z w| + |b|).
+Attention (ops.f32.attention; attention_f32_bound), three launches a chunk of query rows:
+  scores  s = fmaf(q . k, fl32(1 / sqrt D), 0):  ds = C_ACC D e mag + e |s|, + e |s + mask| for the host's sc.add_(mask)
+  softmax cgs_softmax_rows over ld = ceil4(Sk) columns, the pad columns at -inf: its own relative term (softmax_rows
+          at scale 1, cols = ld), and dp / p <= exp(2 max_row ds) - 1 for the scores' error (every t_j = s_j - max
+          moves by at most 2 max ds, and so does the log of the normaliser)
+  output  tol = store + C_ACC (Sk + 1) e (p |v|) + dp |v|     (K = Sk products of the stored p, alpha = 1)
+  A row whose keys are all blocked is NaN on this path: ref = tol = nan, left out of assert_within and checked apart.
 """
 import math
 
@@ -168,6 +201,10 @@ SILU_SLOPE = 1.1         # max |silu'(x)| (1.0998 at x = 2.4)
 EXP2_REL = 2 * E         # v_exp_f32 (softmax2; __expf in silu_f after one multiply by log2 e)
 RCP_REL = 2 * E          # v_rcp_f32 (silu_f)
 RSQRT_REL = 4 * E        # rsqrtf (2 e) of var + eps formed by one division and one addition (e each)
+# The library functions of the fp32 kernels (f32.hip). No copy of ROCm's HIP math accuracy table is installed beside
+# the compiler, so these are supposed as well: 4 ulp for erff, 2 ulp for expf (1 ulp = 2 e).
+ERFF_REL = 8 * E         # erff (gelu_f)
+EXPF_REL = 4 * E         # expf (the SiLU of gn_f32_apply_kernel)
 TINY = {torch.bfloat16: 2.0 ** -126, torch.float16: 2.0 ** -25, torch.float32: 2.0 ** -126}
 
 
@@ -180,8 +217,9 @@ def f64(t):
     return None if t is None else t.detach().to(torch.float64)
 
 
-def _store(ref):
-    return U * ref.abs() * (1 + 2 * U)
+def _store(ref, dtype=torch.bfloat16):
+    ud = u(dtype)
+    return ud * ref.abs() * (1 + 2 * ud)
 
 
 def rel(a, b):
@@ -220,17 +258,23 @@ def _pre_mag(a, w, bias, alpha):
     return pre, mag
 
 
-def gemm_bound(a, w, bias=None, res=None, alpha=1.0, K=None):
-    """out = alpha a w^T + bias + res. a [M, K], w [N, K] (fp8 weights: pass them decoded, the decode is exact)."""
+def _alpha(alpha, dtype):
+    """float32: alpha as the fp32 value cgs_gemm_f32 is passed."""
+    return _f32(alpha) if dtype == torch.float32 else alpha
+
+
+def gemm_bound(a, w, bias=None, res=None, alpha=1.0, K=None, dtype=torch.bfloat16):
+    """out = alpha a w^T + bias + res. a [M, K], w [N, K] (fp8 weights: pass them decoded, the decode is exact).
+    dtype: the type the kernel stores (float32: the fp32 kernels of f32.hip, module docstring)."""
     K = a.shape[-1] if K is None else K
-    pre, mag = _pre_mag(a, w, bias, alpha)
+    pre, mag = _pre_mag(a, w, bias, _alpha(alpha, dtype))
     ref, tol = pre, 0.0
     if res is not None:
         res = f64(res)
         ref = pre + res
         mag = mag + res.abs()
-        tol = U * pre.abs()
-    return ref, _store(ref) + tol + C_ACC * K * E * mag
+        tol = u(dtype) * pre.abs()
+    return ref, _store(ref, dtype) + tol + C_ACC * K * E * mag
 
 
 def _geglu_tol(x1, g, d1, dg):
@@ -280,11 +324,22 @@ def act_ref(pre, act, param=0.0):
     return torch.where(pre >= 0, pre, pre * _f32(param))
 
 
-def _act_tol(pre, d_pre, res, act, param):
+def _gelu_f_err(pre, y):
+    """gelu_f (common.h), 0.5f x (1 + erff(x fl(1 / sqrt 2))), against the exact function (module docstring)."""
+    t = pre / math.sqrt(2.0)
+    d_erf = 2 / math.sqrt(math.pi) * torch.exp(-t * t) * t.abs() * 2 * E + ERFF_REL * torch.erf(t).abs()
+    return 0.5 * pre.abs() * (d_erf + E * torch.erfc(-t)) + 2 * E * y.abs()
+
+
+def _act_tol(pre, d_pre, res, act, param, dtype=torch.bfloat16):
     """(ref, tol) of round(act(pre)) (+ res) for a pre-activation within d_pre of pre (module docstring)."""
     y = act_ref(pre, act, param)
+    if dtype == torch.float32 and act is not None:
+        d_pre = d_pre + E * pre.abs()            # f32.hip: fmaf(acc, alpha, bias) rounds once before the activation
     if act is None:
         slope, err = 1.0, 0.0
+    elif act == "gelu" and dtype == torch.float32:
+        slope, err = GELU_SLOPE, _gelu_f_err(pre, y)
     elif act == "gelu":
         slope, err = GELU_SLOPE, GELU_ABS
     elif act in _SIG_ARG:
@@ -296,18 +351,18 @@ def _act_tol(pre, d_pre, res, act, param):
     ref, d = y, slope * d_pre + err
     if res is not None:
         ref = y + f64(res)
-        d = d + U * y.abs()
-    return ref, _store(ref) + d * (1 + U)
+        d = d + u(dtype) * y.abs()
+    return ref, _store(ref, dtype) + d * (1 + u(dtype))
 
 
-def gemm_act_bound(a, w, bias, res, act, param=0.0, alpha=1.0, K=None, rs=None, cs=None):
+def gemm_act_bound(a, w, bias, res, act, param=0.0, alpha=1.0, K=None, rs=None, cs=None, dtype=torch.bfloat16):
     """out = round(act(alpha a w^T + bias)) (+ res); with rs / cs the pre-activation is lnfold_bound's (w = w2, bias =
-    b2, alpha ignored). The fp32 addition of the residual is part of mag, as in gemm_bound."""
+    b2, alpha ignored). The fp32 addition of the residual is part of mag, as in gemm_bound. dtype: as gemm_bound."""
     K = a.shape[-1] if K is None else K
-    pre, mag = _pre_mag(a, w, bias, alpha) if rs is None else _lnfold_pre_mag(a, w, bias, rs, cs)
+    pre, mag = _pre_mag(a, w, bias, _alpha(alpha, dtype)) if rs is None else _lnfold_pre_mag(a, w, bias, rs, cs)
     if res is not None:
         mag = mag + f64(res).abs()
-    return _act_tol(pre, C_ACC * K * E * mag, res, act, param)
+    return _act_tol(pre, C_ACC * K * E * mag, res, act, param, dtype)
 
 
 def lnfold_bound(a, w2, b2, rs, cs, geglu=False):
@@ -336,25 +391,26 @@ def _conv_pre_mag(x, w, bias, stride, pad, upsample2x, x2):
     return pre, mag, K
 
 
-def conv_act_bound(x, w, bias, res, act, param=0.0, stride=1, pad=0, upsample2x=False, x2=None):
+def conv_act_bound(x, w, bias, res, act, param=0.0, stride=1, pad=0, upsample2x=False, x2=None,
+                   dtype=torch.bfloat16):
     """out = round(act(conv2d(x (cat x2) (nearest 2x), w) + bias)) (+ res) in NCHW: gemm_act_bound on conv_bound's
     pre-activation."""
     pre, mag, K = _conv_pre_mag(x, w, bias, stride, pad, upsample2x, x2)
     if res is not None:
         mag = mag + f64(res).abs()
-    return _act_tol(pre, C_ACC * K * E * mag, res, act, param)
+    return _act_tol(pre, C_ACC * K * E * mag, res, act, param, dtype)
 
 
-def conv_bound(x, w, bias=None, res=None, stride=1, pad=0, upsample2x=False, x2=None):
-    """out = conv2d(x (cat x2) (nearest 2x), w) + bias + res in NCHW; K = Cin kh kw."""
+def conv_bound(x, w, bias=None, res=None, stride=1, pad=0, upsample2x=False, x2=None, dtype=torch.bfloat16):
+    """out = conv2d(x (cat x2) (nearest 2x), w) + bias + res in NCHW; K = Cin kh kw. dtype: as gemm_bound."""
     pre, mag, K = _conv_pre_mag(x, w, bias, stride, pad, upsample2x, x2)
     res = f64(res)
     ref, tol = pre, 0.0
     if res is not None:
         ref = pre + res
         mag = mag + res.abs()
-        tol = U * pre.abs()
-    return ref, _store(ref) + tol + C_ACC * K * E * mag
+        tol = u(dtype) * pre.abs()
+    return ref, _store(ref, dtype) + tol + C_ACC * K * E * mag
 
 
 # ------------------------------------------------------------------------------------------------ attention
@@ -401,6 +457,13 @@ def _silu(pre, d):
     return ref, SILU_SLOPE * d + rel * ref.abs() + 1e-36
 
 
+def _silu_div(pre, d):
+    """o / (1.0f + expf(-o)) (gn_f32_apply_kernel): expf, the addition of 1 and a true division, e each; the error
+    of the denominator is at most that of its exp term. 1e-36: expf overflows below o = -88 and o / inf = 0."""
+    ref = F.silu(pre)
+    return ref, SILU_SLOPE * d + (EXPF_REL + 2 * E) * ref.abs() + 1e-36
+
+
 def _gn_values(x, pre_add, x2):
     x = f64(x)
     if x2 is not None:
@@ -420,8 +483,35 @@ def gn_depth(HW, Cg, ppb):
     return Lb, Lb + 4 + (Cg * nb + 255) // 256 + 9
 
 
-def _gn_stats(x, pre, groups, ppb=None):
-    """fp64 (mean, var) per (n, g) of v = x + pre and their worst-case fp32 errors; all [N, G, 1]."""
+def gn_f32_form(N, HW, C):
+    """(S, P) of cgs_groupnorm_f32 (f32.hip): S = gn_slices(N, HW) pixel slices an image, slice s over the pixels
+    [HW s // S, HW (s + 1) // S); P pixel lanes per float4 channel chunk in gn_f32_partial_kernel."""
+    S = max(1, min((2048 + N - 1) // N, HW // 32))
+    C4 = C // 4
+    return S, 1 if C4 >= 256 else 256 // C4
+
+
+def gn_f32_bounds(N, HW, C):
+    S = gn_f32_form(N, HW, C)[0]
+    return [HW * s // S for s in range(S + 1)]
+
+
+def gn_f32_depth(N, HW, C, G, pre_add=False):
+    """(Lb, L) of the three kernels of cgs_groupnorm_f32. Partial kernel: a lane adds every P-th pixel of its slice,
+    ceil(cnt / P) shifted additions in sequence, + 3 for the rounding of d = v - sft, sum mu and ssq - sum mu; then the
+    P - 1 Chan merges of the pixel lanes in sequence. Finalize kernel: a thread adds ceil(S cpg / 256) partials in
+    sequence, wave_sum (6), the 4-wave sum (3); the M2 pass has the same depth. pre_add: v = fl(x + pre_add) (gn_ld)
+    moves the data by e |v|, one more step of R."""
+    S, P = gn_f32_form(N, HW, C)
+    b = gn_f32_bounds(N, HW, C)
+    cnt = max(b1 - b0 for b0, b1 in zip(b, b[1:]))
+    Lb = (cnt + P - 1) // P + 3
+    return Lb, Lb + (P - 1) + (S * (C // G) + 255) // 256 + 9 + (1 if pre_add else 0)
+
+
+def _gn_stats(x, pre, groups, ppb=None, bounds=None, depth=None):
+    """fp64 (mean, var) per (n, g) of v = x + pre and their worst-case fp32 errors; all [N, G, 1]. The statistics
+    blocks: ppb pixels each with gn_depth's (Lb, L), or the pixel boundaries ``bounds`` with ``depth`` = (Lb, L)."""
     N, C, H, W = x.shape
     v = (x + pre[:, :, None, None]).reshape(N, groups, -1)
     n = v.shape[-1]
@@ -429,13 +519,17 @@ def _gn_stats(x, pre, groups, ppb=None):
     var = ((v - mean) ** 2).mean(-1, keepdim=True)
     dev2 = ((v - mean) ** 2).amax(-1, keepdim=True)
     R = v.abs().amax(-1, keepdim=True) + 3 * (v.amax(-1, keepdim=True) - v.amin(-1, keepdim=True))
-    if ppb is None:
+    if ppb is None and bounds is None:
         Lb = L = n
         E2 = 2 * var + 2 * dev2
     else:
-        Lb, L = gn_depth(H * W, C // groups, ppb)
+        if bounds is None:
+            Lb, L = gn_depth(H * W, C // groups, ppb)
+            bounds = list(range(0, H * W, ppb)) + [H * W]
+        else:
+            Lb, L = depth
         xr = x.reshape(N, C, H * W)
-        d2 = torch.cat([(xr[:, :, p:p + ppb] - xr[:, :, p:p + 1]) ** 2 for p in range(0, H * W, ppb)], -1)
+        d2 = torch.cat([(xr[:, :, p0:p1] - xr[:, :, p0:p0 + 1]) ** 2 for p0, p1 in zip(bounds, bounds[1:]) if p1 > p0], -1)
         E2 = d2.reshape(N, groups, -1).mean(-1, keepdim=True)
     dmean = L * E * R
     dvar = 2 * Lb * E * E2 + 8 * L * E * var + 4 * var.sqrt() * dmean + dmean ** 2
@@ -461,8 +555,20 @@ def _gn_out(x, pre, mean, rstd, dmean, drstd_rel, w, b, silu, dtype):
     mag = x.abs() * a + (mean.abs() + pre.abs()) * a + bet.abs()
     d = a * dmean + zg.abs() * drstd_rel + 6 * E * mag
     if silu:
-        ref, d = _silu(ref, d)
+        ref, d = _silu_div(ref, d) if silu == "div" else _silu(ref, d)
     return ref, _store_dt(ref, d, dtype)
+
+
+def groupnorm_f32_bound(x, groups, w, b, eps, silu, pre_add=None, x2=None):
+    """cgs_groupnorm_f32 on fp32 x [N, C1, H, W] (cat x2): the statistics over the kernel's own slices (gn_f32_form,
+    gn_f32_depth), the stored a = gamma rstd and b = beta - mean a, fmaf(v, a, b) and the SiLU with a division."""
+    x, pre = _gn_values(x, pre_add, x2)
+    N, C, H, W = x.shape
+    n, mean, var, dmean, dvar = _gn_stats(x, pre, groups, bounds=gn_f32_bounds(N, H * W, C),
+                                          depth=gn_f32_depth(N, H * W, C, groups, pre_add is not None))
+    rstd = 1 / torch.sqrt(var + eps)
+    return _gn_out(x, pre, mean, rstd, dmean, 0.5 * dvar / (var + eps) + RSQRT_REL, w, b, "div" if silu else False,
+                   torch.float32)
 
 
 def groupnorm_bound(x, groups, w, b, eps, silu, pre_add=None, x2=None, ppb=None):
@@ -500,10 +606,17 @@ def ln_depth(C):
     return min(C, 64 + 6) if C <= 4096 else (C + 63) // 64 + 6
 
 
-def _ln_stats(x, eps):
-    """Two-pass row statistics of x [rows, C] in fp64 and their worst-case fp32 errors; all [rows, 1]."""
+def ln_f32_depth(C):
+    """ln_f32_kernel (f32.hip), one wave per row: a lane adds ceil(C / 256) float4s in sequence, each summed as
+    (x + y) + (z + w) (2), then wave_sum (6)."""
+    return (C + 255) // 256 + 2 + 6
+
+
+def _ln_stats(x, eps, depth=None):
+    """Two-pass row statistics of x [rows, C] in fp64 and their worst-case fp32 errors; all [rows, 1]. depth: the
+    dependent additions of a row sum where they are not ln_depth's."""
     C = x.shape[-1]
-    L = ln_depth(C)
+    L = ln_depth(C) if depth is None else depth
     mean = x.mean(-1, keepdim=True)
     var = ((x - mean) ** 2).mean(-1, keepdim=True)
     dmean = C_ACC * L * E * x.abs().mean(-1, keepdim=True) + E * mean.abs()
@@ -512,11 +625,11 @@ def _ln_stats(x, eps):
     return mean, rstd, dmean, 0.5 * dvar / (var + eps) + RSQRT_REL
 
 
-def layernorm_bound(x, w=None, b=None, eps=1e-5):
-    """LayerNorm over the last dim; weight and bias optional."""
+def layernorm_bound(x, w=None, b=None, eps=1e-5, depth=None):
+    """LayerNorm over the last dim; weight and bias optional. depth = ln_f32_depth(C) for cgs_layernorm_f32."""
     dtype, shape = x.dtype, x.shape
     x = f64(x).reshape(-1, shape[-1])
-    mean, rstd, dmean, drstd_rel = _ln_stats(x, eps)
+    mean, rstd, dmean, drstd_rel = _ln_stats(x, eps, depth)
     wa = torch.ones(shape[-1], dtype=torch.float64, device=x.device) if w is None else f64(w)
     ba = 0 * wa if b is None else f64(b)
     zw = (x - mean) * rstd * wa
@@ -941,6 +1054,64 @@ def softmax_rows_bound(x, scale):
     return ref, E * ref + TINY[torch.float32] + rel * ref
 
 
+# ------------------------------------------------------------------------------------------------ fp32 attention
+def attention_f32_scores(q, k, heads, mask=None, causal=False, key_padding=None):
+    """(s, ds) [B, H, Sq, Sk]: the fp64 scores ops.f32.attention hands to cgs_softmax_rows and the bound of their
+    error. cgs_gemm_f32 with alpha = fl32(1 / sqrt D): C_ACC D e mag and the rounding of fmaf(acc, alpha, 0); the
+    host's sc.add_(mask) rounds once more; masked_fill(-inf) is exact. The mask is normalised as the host does."""
+    B, Sq, HD = q.shape
+    Sk, D = k.shape[1], HD // heads
+    al = _f32(1.0 / math.sqrt(D))
+    qh = f64(q).reshape(B, Sq, heads, D).transpose(1, 2)
+    kh = f64(k).reshape(B, Sk, heads, D).transpose(1, 2)
+    s = al * (qh @ kh.transpose(-1, -2))
+    ds = C_ACC * D * E * al * (qh.abs() @ kh.abs().transpose(-1, -2)) + E * s.abs()
+    if mask is not None:
+        m = mask
+        if m.dtype == torch.bool:
+            m = torch.zeros(m.shape, dtype=torch.float64, device=m.device).masked_fill(~m, -math.inf)
+        m = f64(m)
+        while m.dim() < 4:
+            m = m.unsqueeze(0) if m.dim() < 3 else m.unsqueeze(1)
+        s = s + m
+        ds = ds + E * torch.where(torch.isfinite(s), s.abs(), torch.zeros_like(s))
+    if causal:
+        s = s.masked_fill(torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1), -math.inf)
+    if key_padding is not None:
+        s = s.masked_fill(~key_padding.bool()[:, None, None, :], -math.inf)
+    return s, ds
+
+
+def attention_f32_bound(q, k, v, heads, mask=None, causal=False, key_padding=None):
+    """ops.f32.attention, q [B, Sq, H D], k / v [B, Sk, H D] -> [B, Sq, H D], composed from its three launches:
+    the scores within ds (attention_f32_scores); cgs_softmax_rows over ld = ceil4(Sk) columns (the pad columns are
+    -inf and add exact zeros): softmax_rows_bound's relative term at scale 1, and dp / p <= exp(2 max_row ds) - 1
+    for scores that move by ds (the shift of the row maximum included); O = P V, K = Sk products of the stored p:
+    tol = store + C_ACC (Sk + 1) e (p |v|) + dp |v|. A row whose keys are all blocked is NaN on this path (the
+    row softmax of -inf): ref = tol = nan there."""
+    B, Sq, HD = q.shape
+    Sk, D = k.shape[1], HD // heads
+    ld = (Sk + 3) // 4 * 4
+    s, ds = attention_f32_scores(q, k, heads, mask, causal, key_padding)
+    fin = torch.isfinite(s)
+    blocked = ~fin.any(-1, keepdim=True)
+    mx = torch.where(blocked, torch.zeros_like(s[..., :1]), s.amax(-1, keepdim=True))
+    t = torch.where(fin, s - mx, torch.full_like(s, -math.inf))
+    e = torch.exp(t)
+    p = e / e.sum(-1, keepdim=True).clamp_min(1e-300)
+    zero = torch.zeros_like(s)
+    ex = torch.where(fin, (s.abs() + 3 * t.abs()) * E + EXP2_REL, zero)
+    rel = ex + (p * ex).sum(-1, keepdim=True) + C_ACC * ld * E + 2 * E
+    dsmax = torch.where(fin, ds, zero).amax(-1, keepdim=True)
+    dp = p * (torch.expm1(2 * dsmax) + E + rel) + torch.where(fin, TINY[torch.float32], 0.0)
+    vh = f64(v).reshape(B, Sk, heads, D).transpose(1, 2)
+    ref = p @ vh
+    tol = _store_dt(ref, C_ACC * (Sk + 1) * E * (p @ vh.abs()) + dp @ vh.abs(), torch.float32)
+    nan = torch.full_like(ref, math.nan)
+    ref, tol = torch.where(blocked, nan, ref), torch.where(blocked, nan, tol)
+    return ref.transpose(1, 2).reshape(B, Sq, HD), tol.transpose(1, 2).reshape(B, Sq, HD)
+
+
 # ------------------------------------------------------------------------------------------------ tome_match
 def tome_bound(a, b):
     """(s, ds) [B, Na, Nb]: the cosine similarity of every src row a_i with every dst row b_j."""
@@ -1013,3 +1184,115 @@ def tome_inputs(B, Na, Nb, C, dtype, device="cpu", seed=0):
         wa[:, -1] = 0
     wa, wb = wa.to(device), wb.to(device)
     return wa[:, :, 8:8 + C], wb[:, :, 8:8 + C]
+
+
+# ------------------------------------------------------------------------------------------------ fp32 kernels (f32.hip)
+F32_ACTS = [None, "gelu", "gelu_tanh", "quick_gelu", "silu", "relu"]
+# (M, N, K) of ops.linear on the 128 x 128 x 32 tile: one row; one past a tile in M, N and K; K % 4 != 0 (the host pads
+# the rows, the kernel keeps its own K); K < 4; K just under a tile; three K tiles
+F32_LINEAR_SHAPES = [(1, 5, 4), (129, 132, 36), (130, 127, 33), (257, 5, 3), (64, 260, 31), (3, 129, 68)]
+# (N, C1, C2, H, W, Cout, k, stride, pad, up2, res)
+F32_CONV_CASES = [(2, 4, 0, 9, 9, 5, 3, 1, 1, False, False), (1, 3, 0, 6, 5, 8, 3, 1, 1, False, True),
+                  (2, 8, 4, 9, 9, 12, 3, 2, 0, False, True), (1, 8, 0, 4, 6, 16, 3, 1, 1, True, False),
+                  (1, 12, 0, 3, 3, 130, 1, 1, 0, False, False), (1, 6, 6, 5, 5, 8, 3, 1, 1, False, False)]
+# (N, C1, C2, G, H, W)
+F32_GN_CASES = [(2, 8, 0, 2, 1, 1), (3, 64, 0, 32, 5, 7), (2, 320, 0, 32, 10, 10), (1, 1280, 0, 32, 8, 8),
+                (2, 1028, 0, 4, 2, 3), (2, 12, 20, 4, 6, 7), (2, 6, 10, 4, 6, 7)]
+F32_LN_C, F32_LN_ROWS = [4, 252, 256, 260, 1280], [1, 5]
+SPIKE = 48.0
+
+
+def mixed_scales(n, g, lo=1e-3, hi=10.0):
+    """n scales log-spaced over lo .. hi in a random order (one scale: 1)."""
+    if n == 1:
+        return torch.ones(1)
+    return torch.logspace(math.log10(lo), math.log10(hi), n)[torch.randperm(n, generator=g)]
+
+
+def f32_gemm_inputs(M, N, K, seed=0, device="cpu"):
+    """fp32 a [M, K] = randn s_m s_k, w [N, K] = randn s_n / sqrt K, bias [N] = randn s_n, res [M, N] = randn s_m s_n, the
+    scales log-spaced over 1e-3 .. 10 and permuted (s_k over 0.03 .. 3). Spikes of +-48 s_m on element K - 1 of every
+    third row and on element 32 of every fourth (the first of the second K tile)."""
+    g = torch.Generator().manual_seed(seed)
+    s_m, s_n, s_k = mixed_scales(M, g), mixed_scales(N, g), mixed_scales(K, g, 0.03, 3.0)
+    a = torch.randn(M, K, generator=g) * s_m[:, None] * s_k[None, :]
+    a[::3, K - 1] = SPIKE * s_m[::3]
+    if K > 32:
+        a[::4, 32] = -SPIKE * s_m[::4]
+    w = torch.randn(N, K, generator=g) * s_n[:, None] / math.sqrt(K)
+    b = torch.randn(N, generator=g) * s_n
+    r = torch.randn(M, N, generator=g) * s_m[:, None] * s_n[None, :]
+    return tuple(t.to(device) for t in (a, w, b, r)) + ((s_m, s_n, s_k),)
+
+
+def f32_conv_inputs(N, C1, C2, H, W, Cout, k, seed=0, device="cpu"):
+    """fp32 NCHW x [N, C1, H, W], x2 [N, C2, H, W] or None, w [Cout, C1 + C2, k, k], bias, the image, input-channel and
+    output-channel scales log-spaced and permuted. Spikes of +-48 s_n: the first and the last pixel of every image
+    (both sides of an image boundary of the implicit GEMM's rows), the channels on both sides of the dual-source
+    seam at the centre pixel, and the weights' last tap carries no smaller weights than the others."""
+    g = torch.Generator().manual_seed(seed)
+    C = C1 + C2
+    s_i, s_c, s_o = mixed_scales(N, g), mixed_scales(C, g, 0.03, 3.0), mixed_scales(Cout, g)
+    x = torch.randn(N, C, H, W, generator=g) * s_i[:, None, None, None] * s_c[None, :, None, None]
+    x[:, 0, 0, 0] = SPIKE * s_i
+    x[:, C - 1, H - 1, W - 1] = -SPIKE * s_i
+    if C2:
+        x[:, C1 - 1, H // 2, W // 2] = SPIKE * s_i
+        x[:, C1, H // 2, W // 2] = -SPIKE * s_i
+    w = torch.randn(Cout, C, k, k, generator=g) * s_o[:, None, None, None] / math.sqrt(C * k * k)
+    b = torch.randn(Cout, generator=g) * s_o
+    x = x.to(device)
+    x1, x2 = (x[:, :C1].contiguous(), x[:, C1:].contiguous()) if C2 else (x, None)
+    return x1, x2, w.to(device), b.to(device), (s_i, s_c, s_o)
+
+
+def f32_gn_inputs(N, C1, C2, H, W, seed=0, device="cpu", shift=0.0):
+    """fp32 x [N, C1, H, W] (x2 [N, C2, H, W]) = shift + randn s_n s_c, gamma = randn s_c', beta = 0.1 randn s_c',
+    pre_add [N, C] = randn s_n s_c; spikes of +-48 s_n s_c on the last pixel of every slice of cgs_groupnorm_f32 and
+    on the channels on both sides of the seam."""
+    g = torch.Generator().manual_seed(seed)
+    C = C1 + C2
+    s_n, s_c, s_g = mixed_scales(N, g), mixed_scales(C, g, 0.03, 3.0), mixed_scales(C, g)
+    sc = s_n[:, None, None] * s_c[None, :, None]
+    x = torch.randn(N, C, H * W, generator=g) * sc
+    for p in gn_f32_bounds(N, H * W, C)[1:]:
+        x[:, (p * 5) % C, p - 1] = SPIKE * sc[:, (p * 5) % C, 0]
+    if C2:
+        x[:, C1 - 1, (H * W) // 2] = SPIKE * sc[:, C1 - 1, 0]
+        x[:, C1, (H * W) // 2] = -SPIKE * sc[:, C1, 0]
+    x = (x + shift).reshape(N, C, H, W)
+    gamma, beta = torch.randn(C, generator=g) * s_g, 0.1 * torch.randn(C, generator=g) * s_g
+    pa = (torch.randn(N, C, generator=g) * sc[:, :, 0]).to(device)
+    x = x.to(device)
+    x1, x2 = (x[:, :C1].contiguous(), x[:, C1:].contiguous()) if C2 else (x, None)
+    return x1, x2, gamma.to(device), beta.to(device), pa
+
+
+def f32_ln_inputs(rows, C, seed=0, device="cpu", shift=0.0):
+    """fp32 x [rows, C] = shift + randn s_r s_c with a spike of 48 s_r on the last element; w = randn s_c', b = 0.1 randn
+    s_c'."""
+    g = torch.Generator().manual_seed(seed)
+    s_r, s_c, s_w = mixed_scales(rows, g), mixed_scales(C, g, 0.03, 3.0), mixed_scales(C, g)
+    x = torch.randn(rows, C, generator=g) * s_r[:, None] * s_c[None, :]
+    x[:, C - 1] = SPIKE * s_r
+    x = x + shift
+    return x.to(device), (torch.randn(C, generator=g) * s_w).to(device), (0.1 * torch.randn(C, generator=g) * s_w).to(device)
+
+
+def f32_attn_inputs(B, heads, Sq, Sk, D, seed=0, device="cpu"):
+    """q, k, v as views of one fused [B, S, 3 H D] tensor (S = max(Sq, Sk)): q = randn, k = randn with a head scale over
+    0.3 .. 3 (flat and peaked rows), v = randn s_h s_d over 1e-3 .. 10 with spikes of +-48 s_h on the last key and
+    on key 32."""
+    g = torch.Generator().manual_seed(seed)
+    HD, S = heads * D, max(Sq, Sk)
+    qkv = torch.randn(B, S, 3 * HD, generator=g)
+    s_k = mixed_scales(heads, g, 0.3, 3.0).repeat_interleave(D)
+    s_h = mixed_scales(heads, g).repeat_interleave(D)
+    s_v = s_h * mixed_scales(HD, g, 0.1, 1.0)
+    qkv[:, :, HD:2 * HD] *= s_k
+    qkv[:, :, 2 * HD:] *= s_v
+    qkv[:, Sk - 1, 2 * HD:] = SPIKE * s_h
+    if Sk > 32:
+        qkv[:, 32, 2 * HD:] = -SPIKE * s_h
+    qkv = qkv.to(device)
+    return qkv[:, :Sq, :HD], qkv[:, :Sk, HD:2 * HD], qkv[:, :Sk, 2 * HD:], s_h

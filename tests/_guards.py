@@ -37,6 +37,13 @@ def _guarded(cuda, numel, slack):
     return buf, buf.clone(), buf.data_ptr() + 2 * GUARD
 
 
+def _guarded32(cuda, numel, slack):
+    """_guarded for 32-bit elements (fp32 outputs): an int32 pattern, the pointer 4 GUARD bytes in."""
+    n = GUARD + numel + slack
+    buf = ((torch.arange(n, device=cuda, dtype=torch.int64) * 2654435761 >> 7) & 0x7FFFFFFF).to(torch.int32)
+    return buf, buf.clone(), buf.data_ptr() + 4 * GUARD
+
+
 def _check_guard(buf, before, keep, dtype, what):
     """``keep``: a bool mask over buf[GUARD:] of the elements the kernel may write. Returns them as ``dtype``."""
     torch.cuda.synchronize()
