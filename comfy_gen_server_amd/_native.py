@@ -134,6 +134,15 @@ KERNEL_SIGNATURES = {
     "cgs_lanczos_u8_v": [_P, _I, _L, _L, _L, _L, _P, _I, _I, _I, _I, _P, _P, _I, _P],
     # K25 one axis of bislerp: x, y, N, C, Ho, Wo, x strides (n, c, h, w), axis, l_in, c1, c2, ratio, dtype in, out
     "cgs_bislerp": [_P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _I, _I, _P, _P, _P, _I, _I, _P],
+    # image filters (csrc/kernels/filter.hip). filter_sep: x, y, tmp (fp32 with y's strides: two launches; or null),
+    # taps_w, taps_h (fp32, device), kw, kh, N, C, H, W, interleave, x strides (n, c, h, w), y strides, border
+    # (0 reflect, 1 replicate, 2 zero), ax, ay, lo, hi, dtype
+    "cgs_filter_sep": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _I, _F, _F, _F, _F,
+                       _I, _P],
+    # x, tmp, y, N, C, H, W, interleave, x strides, tmp / y strides, k, op (0 max, 1 min), dtype
+    "cgs_morph_box": [_P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _I, _I, _I, _P],
+    "cgs_canny_nms": [_P, _P, _P, _I, _I, _I, _F, _F, _P],             # blur, mag, cls(u8), B, H, W, low, high
+    "cgs_hysteresis_sweep": [_P, _I, _I, _I, _P, _P],                  # cls(u8, in place), B, H, W, counter(i32)
     "cgs_vq_nearest": [_P, _P, _P, _P, _I, _I, _I, _I, _P],            # z, codebook, idx(i64), q, M, n, D
     "cgs_grn_nhwc": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],          # x, gamma, beta, y, ws, N, HW, C
     # GRN statistics only (gx / block sums in the v2 ws layout): x, ws, N, HW, C, pre_gelu, dtype

@@ -1,9 +1,10 @@
 """Image nodes (parity: ``comfy_extras/nodes_images.py``, ``nodes_post_processing.py``, ``nodes_compositing.py``,
 ``nodes_morphology.py``, ``nodes_canny.py``).
 
-IMAGE = float [B,H,W,C] in 0..1 (host). Filters run on the compute device when one is present.
+IMAGE = float [B,H,W,C] in 0..1 (host). Filters run on the compute device when one is present, through
+``ops.filter_sep`` / ``ops.morph_box`` / ``ops.canny`` (HIP kernels on device tensors, the torch code on the CPU).
 The reference's morphology and Canny come from kornia, which is not in this image: both are
-re-implemented here in plain torch (grey morphology with a flat square kernel; Canny = 5x5
+re-implemented in the op layer (grey morphology with a flat square kernel; Canny = 5x5
 Gaussian (sigma 1) -> Sobel -> non-maximum suppression -> double threshold -> hysteresis), so
 their outputs are "parity unpinned" against kornia (tests check the defining properties instead).
 """
@@ -18,6 +19,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .. import ops
 from ..runtime import device as dm
 from ..utils import folder_paths
 from ..utils import image as U
@@ -215,15 +217,6 @@ def gaussian_kernel(kernel_size: int, sigma: float, device=None):
     return g / g.sum()
 
 
-def _depthwise(image_bhwc, kernel, radius):
-    c = image_bhwc.shape[-1]
-    x = image_bhwc.movedim(-1, 1)
-    x = F.pad(x, (radius, radius, radius, radius), mode="reflect")
-    k = kernel.to(x.dtype).expand(c, 1, *kernel.shape)
-    y = F.conv2d(x, k, groups=c)
-    return y.movedim(1, -1)
-
-
 class ImageBlur:
     @classmethod
     def INPUT_TYPES(s):
@@ -237,8 +230,11 @@ class ImageBlur:
         if blur_radius == 0:
             return (image,)
         x = image.to(_dev())
-        k = gaussian_kernel(2 * blur_radius + 1, sigma, device=x.device)
-        return (_depthwise(x, k, blur_radius).to(dm.intermediate_device()),)
+        ks = 2 * blur_radius + 1
+        # device: separable taps through cgs_filter_sep; the torch path keeps the dense 2-D kernel
+        y = ops.filter_sep(x, ops.gaussian_taps(ks, sigma, x.device, "unit"), layout="nhwc",
+                           dense=lambda: gaussian_kernel(ks, sigma, device=x.device))
+        return (y.to(dm.intermediate_device()),)
 
 
 class ImageSharpen:
@@ -256,10 +252,16 @@ class ImageSharpen:
         if sharpen_radius == 0:
             return (image,)
         ks = 2 * sharpen_radius + 1
-        k = gaussian_kernel(ks, sigma, device=image.device) * -(alpha * 10)
-        c = ks // 2
-        k[c, c] = k[c, c] - k.sum() + 1.0          # unsharp mask: identity - scaled blur, sums to 1
-        return (_depthwise(image, k, sharpen_radius).clamp(0, 1),)
+
+        def dense():
+            k = gaussian_kernel(ks, sigma, device=image.device) * -(alpha * 10)
+            c = ks // 2
+            k[c, c] = k[c, c] - k.sum() + 1.0          # unsharp mask: identity - scaled blur, sums to 1
+            return k
+        # K = -c G + (1 + c sum(G)) delta with sum(G) = 1: a blur with an axpy epilogue on the device
+        c = alpha * 10
+        return (ops.filter_sep(image, ops.gaussian_taps(ks, sigma, image.device, "unit"), layout="nhwc",
+                               ax=1.0 + c, ay=-c, clamp=(0, 1), dense=dense),)
 
 
 class ImageQuantize:
@@ -432,12 +434,11 @@ class JoinImageWithAlpha:
 
 # ---------------------------------------------------------------- morphology / edges
 def _dilate(x, k):
-    p = k // 2
-    return F.max_pool2d(F.pad(x, (p, k - 1 - p, p, k - 1 - p), mode="replicate"), k, stride=1)
+    return ops.morph_box(x, k, "dilate")
 
 
 def _erode(x, k):
-    return -_dilate(-x, k)
+    return ops.morph_box(x, k, "erode")
 
 
 class Morphology:
@@ -475,45 +476,7 @@ class Morphology:
 
 def canny_edges(img_bchw, low, high):
     """Canny on [B,C,H,W] in 0..1 -> (magnitude, edges) each [B,1,H,W]."""
-    if img_bchw.shape[1] == 3:
-        gray = (0.299 * img_bchw[:, 0] + 0.587 * img_bchw[:, 1] + 0.114 * img_bchw[:, 2])[:, None]
-    else:
-        gray = img_bchw[:, :1]
-    ax = torch.arange(5, dtype=gray.dtype, device=gray.device) - 2
-    g1 = torch.exp(-ax ** 2 / 2.0)
-    g1 = g1 / g1.sum()
-    blur = F.conv2d(F.pad(gray, (2, 2, 2, 2), mode="reflect"), (g1[:, None] * g1[None, :])[None, None])
-    sx = torch.tensor([[-1., 0., 1.], [-2., 0., 2.], [-1., 0., 1.]], dtype=gray.dtype, device=gray.device)
-    p = F.pad(blur, (1, 1, 1, 1), mode="replicate")
-    gx = F.conv2d(p, sx[None, None])
-    gy = F.conv2d(p, sx.t()[None, None])
-    mag = torch.sqrt(gx * gx + gy * gy + 1e-6)
-    ang = torch.rad2deg(torch.atan2(gy, gx)) % 180.0
-    # quantised direction -> neighbour offsets (0, 45, 90, 135 degrees)
-    q = (((ang + 22.5) // 45) % 4).long()
-    mp = F.pad(mag, (1, 1, 1, 1))
-    H, W = mag.shape[-2:]
-
-    def shift(dy, dx):
-        return mp[..., 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
-    offs = [((0, 1), (0, -1)), ((1, 1), (-1, -1)), ((1, 0), (-1, 0)), ((1, -1), (-1, 1))]
-    n1 = torch.zeros_like(mag)
-    n2 = torch.zeros_like(mag)
-    for i, (a, b) in enumerate(offs):
-        sel = q == i
-        n1 = torch.where(sel, shift(*a), n1)
-        n2 = torch.where(sel, shift(*b), n2)
-    nms = torch.where((mag >= n1) & (mag >= n2), mag, torch.zeros_like(mag))
-    strong = nms > high
-    weak = (nms > low) & ~strong
-    edges = strong.float()
-    for _ in range(max(H, W)):            # hysteresis: grow strong edges through weak pixels
-        grown = (F.max_pool2d(edges, 3, stride=1, padding=1) > 0) & weak
-        new = torch.maximum(edges, grown.float())
-        if torch.equal(new, edges):
-            break
-        edges = new
-    return mag, edges
+    return ops.canny(img_bchw, low, high)
 
 
 class Canny:
@@ -527,7 +490,7 @@ class Canny:
     CATEGORY = "image/preprocessors"
 
     def detect_edge(self, image, low_threshold, high_threshold):
-        _, edges = canny_edges(image.to(_dev()).movedim(-1, 1).float(), low_threshold, high_threshold)
+        _, edges = ops.canny(image.to(_dev()).movedim(-1, 1).float(), low_threshold, high_threshold)
         return (edges.to(dm.intermediate_device()).repeat(1, 3, 1, 1).movedim(1, -1),)
 
 

@@ -226,14 +226,13 @@ def attention_with_probs(q, k, v, heads):
 
 
 def gaussian_blur_2d(img, kernel_size, sigma):
-    half = (kernel_size - 1) * 0.5
-    # built on the device: no host->device copy, so SAG's post-CFG hook is hipGraph-capturable
-    t = torch.linspace(-half, half, steps=kernel_size, device=img.device, dtype=torch.float32)
-    pdf = torch.exp(-0.5 * (t / sigma).pow(2))
-    k1 = (pdf / pdf.sum()).to(dtype=img.dtype)
-    k2 = torch.outer(k1, k1).expand(img.shape[-3], 1, kernel_size, kernel_size)
-    p = kernel_size // 2
-    return F.conv2d(F.pad(img, (p, p, p, p), mode="reflect"), k2, groups=img.shape[-3])
+    # taps built on the device: no host->device copy, so SAG's post-CFG hook is hipGraph-capturable
+    taps = ops.gaussian_taps(kernel_size, sigma, img.device, span="pixel")
+
+    def dense():   # the torch path's 2-D kernel: the outer product in the image's dtype
+        k1 = taps.to(dtype=img.dtype)
+        return torch.outer(k1, k1)
+    return ops.filter_sep(img, taps, border="reflect", dense=dense)
 
 
 def create_blur_map(x0, attn, sigma=3.0, threshold=1.0):

@@ -25,4 +25,5 @@ from .core import (  # noqa: F401
     step_advance, vae_out_u8, region_accumulate, region_normalize, clip_embed, pooled_gather,
     layernorm_stats, layernorm_stats_for, lnfold_weights, linear_lnfold, lnfold_available, fourier_filter, tome_match,
     rng_key_scope, lanczos_resize, lanczos_reference, lanczos_tables, bislerp, bislerp_tables,
+    filter_sep, gaussian_taps, morph_box, canny_classes, hysteresis, canny,
 )

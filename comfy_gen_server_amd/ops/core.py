@@ -1756,6 +1756,322 @@ def bislerp(x: torch.Tensor, width: int, height: int) -> torch.Tensor:
     return _bislerp_torch(x, width, height)
 
 
+# Image filters (csrc/kernels/filter.hip): separable blur / sharpen, grey morphology, Canny
+_BORDERS = {"reflect": 0, "replicate": 1, "zero": 2}
+_FILTER_MAX_TAPS = 63
+_FILTER_MAX_INTERLEAVE = 4
+_FILTER_TWO_LAUNCH_TAPS = 33   # from this many taps on an axis the two-launch form is the faster one (profiles/r11)
+_MORPH_MAX_WINDOW = 1023
+_HYSTERESIS_BATCH = 8      # sweeps between two reads of the device counters
+
+
+def gaussian_taps(k: int, sigma: float, device=None, span: str = "unit") -> torch.Tensor:
+    """``k`` normalised fp32 Gaussian taps, built with torch ops on ``device`` (no host table, so a caller
+    under hipGraph capture stays capturable). ``unit`` samples ``linspace(-1, 1, k)`` (the image nodes'
+    convention: sigma is relative to the radius), ``pixel`` samples ``linspace(-(k-1)/2, (k-1)/2, k)``."""
+    if span == "unit":
+        lin = torch.linspace(-1, 1, k, device=device, dtype=torch.float32)
+        g = torch.exp(-(lin * lin) / (2.0 * sigma * sigma))
+    elif span == "pixel":
+        half = (k - 1) * 0.5
+        t = torch.linspace(-half, half, steps=k, device=device, dtype=torch.float32)
+        g = torch.exp(-0.5 * (t / sigma).pow(2))
+    else:
+        raise ValueError(f"gaussian_taps: span {span!r} (unit | pixel)")
+    return g / g.sum()
+
+
+def _logical_nchw(x: torch.Tensor, layout: str) -> torch.Tensor:
+    if layout == "nhwc":
+        return x.movedim(-1, -3)
+    if layout != "nchw":
+        raise ValueError(f"layout {layout!r} (nchw | nhwc)")
+    return x
+
+
+def _interleave(xl: torch.Tensor, y_strides) -> int:
+    """Channel interleave of the filter kernels: C when the channels of x or y are adjacent in memory (NHWC)."""
+    C = xl.shape[1]
+    return C if 1 < C <= _FILTER_MAX_INTERLEAVE and (xl.stride(1) == 1 or y_strides[1] == 1) else 1
+
+
+def _alloc_like_layout(xl: torch.Tensor, layout: str, dtype=None):
+    """(y in the caller's layout, contiguous; its logical [N, C, H, W] view)"""
+    N, C, H, W = xl.shape
+    dtype = dtype or xl.dtype
+    if layout == "nhwc":
+        y = torch.empty((N, H, W, C), device=xl.device, dtype=dtype)
+        return y, y.movedim(-1, 1)
+    y = torch.empty((N, C, H, W), device=xl.device, dtype=dtype)
+    return y, y
+
+
+def _filter_sep_torch(x, taps_w, taps_h, border, layout, ax, ay, clamp, dense):
+    """The dense 2-D form: ``F.pad`` then a depthwise ``F.conv2d`` with K = ax * delta + ay * (t_h (x) t_w), or
+    with ``dense`` (the 2-D kernel itself, or a callable that builds it) where the caller has one."""
+    xl = _logical_nchw(x, layout)
+    lead = xl.shape[:-3]
+    if xl.dim() != 4:
+        xl = xl.reshape((-1,) + tuple(xl.shape[-3:]))
+    c = xl.shape[1]
+    if dense is not None:
+        kernel = dense() if callable(dense) else dense
+    else:
+        kernel = ay * torch.outer(taps_h, taps_w)
+        kernel[taps_h.numel() // 2, taps_w.numel() // 2] += ax
+    rh, rw = kernel.shape[0] // 2, kernel.shape[1] // 2
+    if border == "zero":
+        xp = F.pad(xl, (rw, rw, rh, rh))
+    else:
+        xp = F.pad(xl, (rw, rw, rh, rh), mode=border)
+    k = kernel.to(xp.dtype).expand(c, 1, *kernel.shape)
+    y = F.conv2d(xp, k, groups=c)
+    if clamp is not None:
+        y = y.clamp(clamp[0], clamp[1])
+    if len(lead) != 1:
+        y = y.reshape(tuple(lead) + tuple(y.shape[-3:]))
+    return y.movedim(-3, -1) if layout == "nhwc" else y
+
+
+def _filter_sep_hip(xl, taps_w, taps_h, border, layout, ax, ay, clamp, two_launch=None):
+    """One ``cgs_filter_sep`` call. ``two_launch`` (default: by the tap count) runs the horizontal taps into an fp32
+    temporary and the vertical taps out of it; both forms give the same bits."""
+    N, C, H, W = xl.shape
+    y, yl = _alloc_like_layout(xl, layout)
+    if y.numel() == 0:
+        return y
+    tw = taps_w.to(device=xl.device, dtype=torch.float32).contiguous()
+    th = tw if taps_h is taps_w else taps_h.to(device=xl.device, dtype=torch.float32).contiguous()
+    lo, hi = (float("-inf"), float("inf")) if clamp is None else (float(clamp[0]), float(clamp[1]))
+    if two_launch is None:
+        two_launch = max(tw.numel(), th.numel()) >= _FILTER_TWO_LAUNCH_TAPS
+    tmp = torch.empty(y.shape, device=y.device, dtype=torch.float32) if two_launch else None
+    _check(_lib().cgs_filter_sep(xl.data_ptr(), y.data_ptr(), tmp.data_ptr() if two_launch else None, tw.data_ptr(),
+                                 th.data_ptr(), tw.numel(), th.numel(), N, C, H, W, _interleave(xl, yl.stride()), *xl.stride(), *yl.stride(),
+                                 _BORDERS[border], float(ax), float(ay), lo, hi, _DT[xl.dtype], _stream()),
+           "cgs_filter_sep")
+    return y
+
+
+def filter_sep(x: torch.Tensor, taps_w: torch.Tensor, taps_h: torch.Tensor | None = None, *, border: str = "reflect",
+               layout: str = "nchw", ax: float = 0.0, ay: float = 1.0, clamp=None, dense=None) -> torch.Tensor:
+    """``clamp(ax * x + ay * ((taps_h (x) taps_w) * x))``: separable 2-D correlation per channel with a fused
+    axpy / clamp epilogue (gaussian blur: ax 0, ay 1; unsharp mask: ax 1 + c, ay -c). ``taps_h`` defaults to
+    ``taps_w``; tap counts are odd. ``border`` is ``reflect`` (F.pad's, radius < extent), ``replicate`` or ``zero``.
+    ``layout`` names the axes of ``x`` (``nchw`` | ``nhwc``); the result is contiguous in that layout.
+    Device path: one ``cgs_filter_sep`` launch that reads ``x`` through its strides, fp32 taps (device tensors) and
+    accumulation. The torch path is the dense ``F.pad`` + depthwise ``F.conv2d``; ``dense`` (a 2-D kernel or a
+    callable returning it, the epilogue's ax / ay already folded in) replaces the outer product there, for callers
+    whose CPU results are pinned to a kernel they build themselves. Taps longer than 63, non-float dtypes and
+    inputs that are not 4-D go through ``vendor_fallback``."""
+    if border not in _BORDERS:
+        raise ValueError(f"filter_sep: border {border!r} (reflect | replicate | zero)")
+    taps_h = taps_w if taps_h is None else taps_h
+    kw, kh = int(taps_w.numel()), int(taps_h.numel())
+    if taps_w.dim() != 1 or taps_h.dim() != 1 or kw % 2 == 0 or kh % 2 == 0:
+        raise ValueError(f"filter_sep: taps must be 1-D with an odd count, got {kw} and {kh}")
+    xl = _logical_nchw(x, layout)
+    if x.dim() < 3:
+        raise ValueError(f"filter_sep: input of {x.dim()} dimensions")
+    H, W = xl.shape[-2], xl.shape[-1]
+    if border == "reflect" and (kw // 2 >= W or kh // 2 >= H):
+        raise ValueError(f"filter_sep: reflect border needs a radius below the extent: radii ({kh // 2}, {kw // 2}) "
+                         f"on {H}x{W}")
+    be = backend_for("filter", x, "cgs_filter_sep")
+    if be == "hip":
+        if x.dim() == 4 and x.dtype in _DT and kw <= _FILTER_MAX_TAPS and kh <= _FILTER_MAX_TAPS:
+            count("filter", "hip")
+            return _filter_sep_hip(xl, taps_w, taps_h, border, layout, ax, ay, clamp)
+        vendor_fallback("filter", f"dtype {x.dtype}, {x.dim()}-D, taps {kh}x{kw}")
+    else:
+        count("filter", "torch")
+    return _filter_sep_torch(x, taps_w, taps_h, border, layout, ax, ay, clamp, dense)
+
+
+def _dilate_torch(x, k):
+    p = k // 2
+    return F.max_pool2d(F.pad(x, (p, k - 1 - p, p, k - 1 - p), mode="replicate"), k, stride=1)
+
+
+def _erode_torch(x, k):
+    return -_dilate_torch(-x, k)
+
+
+def morph_box(x: torch.Tensor, k: int, op: str = "dilate", layout: str = "nchw") -> torch.Tensor:
+    """k x k box maximum (``dilate``) or minimum (``erode``): ``F.max_pool2d`` after replicate padding
+    ``(k // 2, k - 1 - k // 2)``, i.e. the extremum over the window ``[i - k//2, i + k-1 - k//2]`` clamped to the
+    image, even k and k beyond the image included. Device path: ``cgs_morph_box`` (rows, then columns, window
+    extrema by doubling in LDS: O(log k) per pixel), exact in every dtype; x is read through its strides."""
+    if op not in ("dilate", "erode"):
+        raise ValueError(f"morph_box: op {op!r} (dilate | erode)")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"morph_box: k = {k}")
+    xl = _logical_nchw(x, layout)
+    be = backend_for("morph", x, "cgs_morph_box")
+    if be == "hip":
+        ok = x.dim() == 4 and x.dtype in _DT and xl.shape[-2] <= 65535
+        if ok:
+            p, q = k // 2, k - 1 - k // 2
+            ok = all(min(p, L - 1) + min(q, L - 1) + 1 <= _MORPH_MAX_WINDOW for L in xl.shape[-2:] if L > 0)
+        if ok:
+            count("morph", "hip")
+            N, C, H, W = xl.shape
+            y, yl = _alloc_like_layout(xl, layout)
+            if y.numel() == 0:
+                return y
+            tmp = torch.empty_like(y)
+            _check(_lib().cgs_morph_box(xl.data_ptr(), tmp.data_ptr(), y.data_ptr(), N, C, H, W,
+                                        _interleave(xl, yl.stride()), *xl.stride(), *yl.stride(), k,
+                                        0 if op == "dilate" else 1, _DT[xl.dtype], _stream()), "cgs_morph_box")
+            return y
+        vendor_fallback("morph", f"dtype {x.dtype}, {x.dim()}-D, k={k} on {tuple(xl.shape[-2:])}")
+    else:
+        count("morph", "torch")
+    y = _dilate_torch(xl, k) if op == "dilate" else _erode_torch(xl, k)
+    return y.movedim(-3, -1) if layout == "nhwc" else y
+
+
+def _canny_gray(img_bchw):
+    if img_bchw.shape[1] == 3:
+        return (0.299 * img_bchw[:, 0] + 0.587 * img_bchw[:, 1] + 0.114 * img_bchw[:, 2])[:, None]
+    return img_bchw[:, :1]
+
+
+def _canny_nms_torch(img_bchw, low, high):
+    """Canny up to the double threshold -> (mag, strong, weak)."""
+    gray = _canny_gray(img_bchw)
+    ax = torch.arange(5, dtype=gray.dtype, device=gray.device) - 2
+    g1 = torch.exp(-ax ** 2 / 2.0)
+    g1 = g1 / g1.sum()
+    blur = F.conv2d(F.pad(gray, (2, 2, 2, 2), mode="reflect"), (g1[:, None] * g1[None, :])[None, None])
+    sx = torch.tensor([[-1., 0., 1.], [-2., 0., 2.], [-1., 0., 1.]], dtype=gray.dtype, device=gray.device)
+    p = F.pad(blur, (1, 1, 1, 1), mode="replicate")
+    gx = F.conv2d(p, sx[None, None])
+    gy = F.conv2d(p, sx.t()[None, None])
+    mag = torch.sqrt(gx * gx + gy * gy + 1e-6)
+    ang = torch.rad2deg(torch.atan2(gy, gx)) % 180.0
+    # quantised direction -> neighbour offsets (0, 45, 90, 135 degrees)
+    q = (((ang + 22.5) // 45) % 4).long()
+    mp = F.pad(mag, (1, 1, 1, 1))
+    H, W = mag.shape[-2:]
+
+    def shift(dy, dx):
+        return mp[..., 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+    offs = [((0, 1), (0, -1)), ((1, 1), (-1, -1)), ((1, 0), (-1, 0)), ((1, -1), (-1, 1))]
+    n1 = torch.zeros_like(mag)
+    n2 = torch.zeros_like(mag)
+    for i, (a, b) in enumerate(offs):
+        sel = q == i
+        n1 = torch.where(sel, shift(*a), n1)
+        n2 = torch.where(sel, shift(*b), n2)
+    nms = torch.where((mag >= n1) & (mag >= n2), mag, torch.zeros_like(mag))
+    strong = nms > high
+    weak = (nms > low) & ~strong
+    return mag, strong, weak
+
+
+def _hysteresis_torch(strong, weak):
+    H, W = strong.shape[-2:]
+    edges = strong.float()
+    for _ in range(max(H, W)):            # hysteresis: grow strong edges through weak pixels
+        grown = (F.max_pool2d(edges, 3, stride=1, padding=1) > 0) & weak
+        new = torch.maximum(edges, grown.float())
+        if torch.equal(new, edges):
+            break
+        edges = new
+    return edges
+
+
+def _canny_classes_hip(img_bchw, low, high):
+    gray = _canny_gray(img_bchw)
+    taps = gaussian_taps(5, 1.0, gray.device, "pixel")
+    blur = _filter_sep_hip(gray, taps, taps, "reflect", "nchw", 0.0, 1.0, None)
+    B, _, H, W = blur.shape
+    mag = torch.empty_like(blur)
+    cls = torch.empty((B, 1, H, W), device=blur.device, dtype=torch.uint8)
+    if blur.numel():
+        _check(_lib().cgs_canny_nms(blur.data_ptr(), mag.data_ptr(), cls.data_ptr(), B, H, W, float(low), float(high),
+                                    _stream()), "cgs_canny_nms")
+    return mag, cls
+
+
+def _hysteresis_hip(cls, info=None):
+    c = cls.contiguous().clone()
+    H, W = c.shape[-2:]
+    B = c.numel() // max(H * W, 1)
+    sweeps = batches = 0
+    while c.numel() and sweeps < H * W:   # every sweep that changes anything promotes a pixel: H * W bounds them
+        counters = torch.zeros(_HYSTERESIS_BATCH, device=c.device, dtype=torch.int32)
+        for i in range(_HYSTERESIS_BATCH):
+            _check(_lib().cgs_hysteresis_sweep(c.data_ptr(), B, H, W, counters.data_ptr() + 4 * i, _stream()),
+                   "cgs_hysteresis_sweep")
+        sweeps += _HYSTERESIS_BATCH
+        batches += 1
+        if int(counters[-1].item()) == 0:   # one read per batch; a sweep that promoted nothing is the fixed point
+            break
+    if info is not None:
+        info.update(sweeps=sweeps, batches=batches)
+    return (c == 2).to(torch.float32)
+
+
+def _canny_hip_ok(img):
+    s = img.shape
+    return (img.dim() == 4 and img.dtype == torch.float32 and min(s[-2:]) > 2 and s[0] <= 65535 and s[-2] <= 32 * 65535
+            and img.numel() > 0)
+
+
+def canny_classes(img_bchw: torch.Tensor, low: float, high: float):
+    """Canny up to the double threshold: ``(mag [B,1,H,W] fp32, classes [B,1,H,W] uint8)`` with class 2 where the
+    non-maximum-suppressed magnitude exceeds ``high``, 1 where it exceeds ``low``, else 0. Gray -> 5-tap sigma-1
+    Gaussian (reflect) -> Sobel (replicate) -> suppression along the direction quantised to 0/45/90/135 degrees.
+    Device path: ``cgs_filter_sep`` then ``cgs_canny_nms``."""
+    be = backend_for("canny", img_bchw, "cgs_canny_nms")
+    if be == "hip":
+        if _canny_hip_ok(img_bchw):
+            count("canny", "hip")
+            return _canny_classes_hip(img_bchw, low, high)
+        vendor_fallback("canny", f"dtype {img_bchw.dtype}, shape {tuple(img_bchw.shape)}")
+    else:
+        count("canny", "torch")
+    mag, strong, weak = _canny_nms_torch(img_bchw, low, high)
+    return mag, strong.to(torch.uint8) * 2 + weak.to(torch.uint8)
+
+
+def hysteresis(cls_u8: torch.Tensor, info: dict | None = None) -> torch.Tensor:
+    """Edges (float 0 / 1) of a class map: the class-2 pixels plus every class-1 pixel 8-connected to one through
+    class-1 pixels. Device path: ``cgs_hysteresis_sweep`` launches (each runs every tile to its own fixed point)
+    until a sweep promotes nothing; the device counters are read once per batch of sweeps, and ``info`` receives
+    the number of sweeps and batches. The device result is the full fixed point; the torch path keeps its
+    reference loop, which stops after max(H, W) rounds of one-pixel growth."""
+    be = backend_for("canny", cls_u8, "cgs_hysteresis_sweep")
+    if be == "hip":
+        if cls_u8.dtype == torch.uint8 and cls_u8.dim() >= 2 and cls_u8.shape[-2] <= 32 * 65535 \
+                and cls_u8.numel() // max(cls_u8.shape[-2] * cls_u8.shape[-1], 1) <= 65535:
+            count("canny", "hip")
+            return _hysteresis_hip(cls_u8, info)
+        vendor_fallback("canny", f"hysteresis on dtype {cls_u8.dtype}, shape {tuple(cls_u8.shape)}")
+    else:
+        count("canny", "torch")
+    return _hysteresis_torch(cls_u8 == 2, cls_u8 == 1)
+
+
+def canny(img_bchw: torch.Tensor, low: float, high: float):
+    """Canny on ``[B, C, H, W]`` in 0..1 -> ``(magnitude, edges)``, each ``[B, 1, H, W]`` (edges float 0 / 1):
+    ``canny_classes`` then ``hysteresis``, counted once as ``canny``."""
+    be = backend_for("canny", img_bchw, "cgs_canny_nms")
+    if be == "hip":
+        if _canny_hip_ok(img_bchw):
+            count("canny", "hip")
+            mag, cls = _canny_classes_hip(img_bchw, low, high)
+            return mag, _hysteresis_hip(cls)
+        vendor_fallback("canny", f"dtype {img_bchw.dtype}, shape {tuple(img_bchw.shape)}")
+    else:
+        count("canny", "torch")
+    mag, strong, weak = _canny_nms_torch(img_bchw, low, high)
+    return mag, _hysteresis_torch(strong, weak)
+
+
 def clip_embed(ids: torch.Tensor, tok_weight: torch.Tensor, pos_weight: torch.Tensor) -> torch.Tensor:
     """``tok_weight[ids] + pos_weight[:S]`` (K26: CLIP token + position embedding, one kernel)."""
     B, S = ids.shape
