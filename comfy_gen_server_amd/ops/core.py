@@ -30,6 +30,12 @@ EPI_SILU_IN = 8   # reserved
 EPI_LNFOLD = 8    # (C side: MC_EPI_LNFOLD; the LN-folded entry points add it themselves)
 EPI_GELU = 32     # GELU(acc + bias) before the residual (v6 ACT kernel, mc::tile family, skinny); with a
 #                   CgsAct code in bits 8-10 (``ACT_CODES[name] << 8``) that activation instead of the erf GELU
+EPI_F32OUT = 16   # fp32 C (the wide-attention score GEMM)
+
+# Autotune name -> GemmVariant of csrc/kernels/gemm_args.h (the names of data/tune_mi355x.json). "hip" and the
+# LN-folded GEMM's "v7" mean different numbers at different sites and are written there.
+GEMM_VARIANTS = {"v4": 4, "v5": 5, "v6": 6, "v7": 7, "v8": 8, "v10": 10, "v11": 11, "v12": 12, "v13": 13, "v14": 14,
+                 "w6": 16, "w6n160": 17, "v6m128": 19, "v6w4": 20}
 
 # hipBLASLt (through ATen) as a GEMM autotune candidate: off unless explicitly requested -- the
 # hand-written MFMA kernels (v5/v6/v7) are the device GEMMs; profiles/r02_gemm_table_v7.md has the
@@ -61,6 +67,26 @@ def _ptr(t):
 # ----------------------------------------------------------------------------------------------
 # GEMM family
 # ----------------------------------------------------------------------------------------------
+W6, W6_160 = GEMM_VARIANTS["w6"], GEMM_VARIANTS["w6n160"]   # gemm_w6.hip (256 / 160-wide tiles) through cgs_gemm_bf16_v / _lnfold_v
+V6_M128 = GEMM_VARIANTS["v6m128"]    # v6 with 128 x 160 tiles (pq::run NI = 2): the short-M grids
+V6_W4 = GEMM_VARIANTS["v6w4"]        # v6 with 128 x 80 tiles, 4 waves, two workgroups per CU (pq::run NW = 4): batch-1 grids
+# small-tile GEMM variants (gemm.hip gemm_v8_launch): 10 / 11 = 64x128 / 128x64 with a 4-stage ring,
+# 12 / 13 = the same with 6 stages, 14 = 128x128 with 5 stages
+_SMALL_NAMES = {n: GEMM_VARIANTS[n] for n in ("v10", "v11", "v12", "v13", "v14")}
+# split-K forms of the v8 family (cgs_gemm_bf16_splitk): autotune name -> (tile variant, slices)
+_SPLITK = {"sk2v8": (8, 2), "sk4v8": (8, 4), "sk2v10": (10, 2), "sk4v10": (10, 4), "sk2v11": (11, 2),
+           "sk4v11": (11, 4), "sk8v8": (8, 8)}
+# autotune candidates are (name, variant) pairs: those of the table, by name
+_CAND = {n: (n, v) for n, v in GEMM_VARIANTS.items()}
+_SMALL_CANDS = [_CAND[n] for n in _SMALL_NAMES]
+
+
+def _timed(cands, run):
+    """The (name, callable) list ``autotune.choose`` takes, from (name, variant) pairs: ``run(variant)`` runs the
+    op once. The variant of the name it returns is ``dict(cands)[name]``, so the two cannot disagree."""
+    return [(n, (lambda v=v: run(v))) for n, v in cands]
+
+
 _V7WS: dict = {}
 _V7_SPLIT = os.environ.get("CGS_V7_SPLIT", "1") != "0"
 
@@ -86,6 +112,57 @@ def _skinny_ws(M: int, N: int, K: int, device):
             and os.environ.get("CGS_SKINNY_SPLIT", "1") != "0" else 0
         _SKWS[(M, N, K)] = n
     return torch.empty(n, dtype=torch.uint8, device=device) if n else None
+
+
+def _gemm_launch(a, w, out, bias, r, M, N, K, epi, variant, *, lda=None, ldw=None, ldc=None, alpha=1.0, rs=None,
+                 cs=None, part=None, hw=None, skinny=False, v7ws=False, device=None, label=None):
+    """One bf16 GEMM launch, the operands as in ``GemmArgs`` (csrc/kernels/gemm_args.h): ``a`` / ``w`` / ``out``
+    (tensors or raw addresses), bias, residual ``r`` (dense rows of C's width), row strides (default K / K / N),
+    ``epi`` and ``alpha`` verbatim. The only caller of the exported ``cgs_gemm_*`` launchers besides the fp8-weight
+    one; the operands pick the entry, in this order:
+      * ``variant`` a ``_SPLITK`` name: cgs_gemm_bf16_splitk, its fp32 partials allocated here (LN-folded with
+        ``rs`` / ``cs``: ``epi`` then carries EPI_LNFOLD);
+      * ``hw`` (rows per image): cgs_gemm_bf16_gelu_gns writes the GRN partials ``part`` (``epi`` with EPI_LNFOLD);
+      * ``part`` alone: cgs_gemm_bf16_rowstats_v writes the LayerNorm partials;
+      * ``rs`` / ``cs``: cgs_gemm_bf16_lnfold_v (``epi`` without EPI_LNFOLD, the entry adds it), with the v7 tail
+        workspace for the variants that may run v7 (-1, 7);
+      * ``skinny``: cgs_gemm_skinny_ws where M <= 128 on an automatic variant has a split-K workspace;
+      * variant 7 with a tail workspace (``v7ws``: also without one): cgs_gemm_bf16_v7ws; else cgs_gemm_bf16_v.
+    ``label``: the name a failure reports, where it is not the entry's."""
+    dev = a.device if device is None else device
+    lda, ldw, ldc = lda or K, ldw or K, ldc or N
+    head = (a if type(a) is int else a.data_ptr(), w if type(w) is int else w.data_ptr(),
+            out if type(out) is int else out.data_ptr(), None if bias is None else bias.data_ptr(),
+            None if r is None else r.data_ptr())
+    tail = (M, N, K, lda, ldw, ldc, ldc if r is not None else 0, epi, alpha)
+    lib, st, name = _lib(), _stream(), "cgs_gemm_bf16"
+    if isinstance(variant, str):
+        name, (tile, s) = "cgs_gemm_bf16_splitk", _SPLITK[variant]
+        ws = torch.empty(s * M * N, device=dev, dtype=torch.float32)
+        err = lib.cgs_gemm_bf16_splitk(*head, _ptr(rs), _ptr(cs), *tail, s, tile, ws.data_ptr(), ws.numel() * 4, st)
+    elif hw is not None:
+        name = "cgs_gemm_bf16_gelu_gns"
+        err = lib.cgs_gemm_bf16_gelu_gns(*head[:4], _ptr(rs), _ptr(cs), M, N, K, lda, ldw, ldc, epi, part.data_ptr(),
+                                         hw, st)
+    elif part is not None:
+        name = "cgs_gemm_bf16_rowstats_v"
+        err = lib.cgs_gemm_bf16_rowstats_v(*head, *tail, part.data_ptr(), variant, st)
+    elif rs is not None:
+        name = "cgs_gemm_bf16_lnfold_v"
+        ws = _v7_ws(M, N, K, dev) if variant in (-1, 7) else None
+        err = lib.cgs_gemm_bf16_lnfold_v(*head[:4], rs.data_ptr(), cs.data_ptr(), M, N, K, lda, ldw, ldc, epi,
+                                         _ptr(ws), 0 if ws is None else ws.numel(), variant, st)
+    elif (skinny and M <= 128 and variant in (-1, -2) and K % 32 == 0 and (head[0] | head[1]) % 16 == 0
+          and (ws := _skinny_ws(M, N, K, dev)) is not None):     # split-K slices when N / 16 workgroups underfill
+        name = "cgs_gemm_skinny_ws"
+        err = lib.cgs_gemm_skinny_ws(*head, *tail, ws.data_ptr(), ws.numel(), st)
+    elif variant == 7 and ((ws := _v7_ws(M, N, K, dev)) is not None or v7ws):
+        name = "cgs_gemm_bf16_v7ws"
+        err = lib.cgs_gemm_bf16_v7ws(*head, *tail, _ptr(ws), 0 if ws is None else ws.numel(), st)
+    else:
+        err = lib.cgs_gemm_bf16_v(*head, *tail, variant, st)
+    _check(err, label or name)
+    return out
 
 
 # D = 64 self-attention grids below this many 256-row workgroups are tuned among the small-grid forms
@@ -157,76 +234,55 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
             o = dst if dst is not None else torch.empty((M, N), device=x.device, dtype=x.dtype)
             if isinstance(variant, str):                       # split-K (batch-1 grids)
                 return _splitk_run(a, w, o, bias, r, None, None, M, N, K, epi, variant)
-            if (final and row_stats and variant in (6, 19, 20) and act is None and N % 160 == 0 and K % 64 == 0
+            part = None
+            if (final and row_stats and variant in (6, V6_M128, V6_W4) and act is None and N % 160 == 0 and K % 64 == 0
                     and K >= 128 and _RSO and _native.has_kernel("cgs_gemm_bf16_rowstats_v")):
                 part = torch.empty((M, N // 80, 2), device=x.device, dtype=torch.float32)
-                _check(_lib().cgs_gemm_bf16_rowstats_v(a.data_ptr(), w.data_ptr(), o.data_ptr(), _ptr(bias), _ptr(r),
-                                                       M, N, K, a.stride(0), K, N, N if r is not None else 0, epi,
-                                                       1.0, part.data_ptr(), variant, _stream()),
-                       "cgs_gemm_bf16_rowstats_v")
                 rs_part.append(part)
-                return o
-            if (M <= 128 and variant in (-1, -2) and K % 32 == 0 and (a.data_ptr() | w.data_ptr()) % 16 == 0
-                    and not act2):     # (the split-K reduce knows the erf GELU only)
-                ws = _skinny_ws(M, N, K, x.device)     # split-K slices when N / 16 workgroups underfill
-                if ws is not None:
-                    _check(_lib().cgs_gemm_skinny_ws(a.data_ptr(), w.data_ptr(), o.data_ptr(), _ptr(bias), _ptr(r),
-                                                     M, N, K, a.stride(0), K, N, N if r is not None else 0, epi, 1.0,
-                                                     ws.data_ptr(), ws.numel(), _stream()), "cgs_gemm_skinny_ws")
-                    return o
-            ws = _v7_ws(M, N, K, x.device) if variant == 7 else None
-            if ws is not None:
-                _check(_lib().cgs_gemm_bf16_v7ws(a.data_ptr(), w.data_ptr(), o.data_ptr(), _ptr(bias), _ptr(r),
-                                                 M, N, K, a.stride(0), K, N, N if r is not None else 0, epi, 1.0,
-                                                 ws.data_ptr(), ws.numel(), _stream()), "cgs_gemm_bf16_v7ws")
-                return o
-            _check(_lib().cgs_gemm_bf16_v(a.data_ptr(), w.data_ptr(), o.data_ptr(), _ptr(bias), _ptr(r),
-                                          M, N, K, a.stride(0), K, N, N if r is not None else 0, epi, 1.0,
-                                          variant, _stream()), "cgs_gemm_bf16")
-            return o
+            return _gemm_launch(a, w, o, bias, r, M, N, K, epi, variant, lda=a.stride(0), part=part,
+                                skinny=not act2)     # (the skinny split-K reduce knows the erf GELU only)
 
         def run_lib():
             y = F.linear(a, w, bias)
             return y if r is None else y.add_(r)
 
-        choice = "hip"
+        # below the tuning thresholds: "hip" = -2, the process-wide choice (cgs_gemm_set_variant; auto unless set)
+        choice, cands = "hip", [("hip", -2)]
         # M <= 128 (one prompt through CLIP, time-embedding projections): the skinny kernel ("hip" ->
         # auto), weight-bandwidth bound; the big-tile kernels are not candidates there
         if act2 and M * N * K >= (1 << 27) and M > 128:
             cands = []
             if K % 64 == 0 and K >= 128:
-                cands.append(("v6", lambda: run_hip(6)))
-            cands += [("v4", lambda: run_hip(4)), ("v8", lambda: run_hip(8))]
+                cands.append(_CAND["v6"])
+            cands += [_CAND["v4"], _CAND["v8"]]
             if _underfilled(M, N):
-                cands += [(f"v{v}", (lambda v=v: run_hip(v))) for v in _SMALL_TILE]
-            cands.append(("hip", lambda: run_hip(-1)))
-            choice = autotune.choose(("gemm", M, N, K, epi), cands, default="hip")
+                cands += _SMALL_CANDS
+            cands.append(("hip", -2))
+            choice = autotune.choose(("gemm", M, N, K, epi), _timed(cands, run_hip), default="hip")
         elif not act2 and M * N * K >= (1 << 27) and (M > 128 or K % 32):
             cands = []
             if K % 64 == 0 and N % 8 == 0:
                 if K >= 128 and not gelu:
-                    cands.append(("v7", lambda: run_hip(7)))
+                    cands.append(_CAND["v7"])
                 if not gelu:
-                    cands.append(("v5", lambda: run_hip(5)))
+                    cands.append(_CAND["v5"])
                 if K >= 128 or not gelu:
-                    cands.append(("v6", lambda: run_hip(6)))
-            cands += _w6_cands(M, N, K, epi, run_hip)     # one wave per SIMD, full-line DMA, persistent
+                    cands.append(_CAND["v6"])
+            cands += _w6_cands(M, N, K, epi)     # one wave per SIMD, full-line DMA, persistent
             if K % 32 == 0 and N % 8 == 0:
-                cands.append(("v4", lambda: run_hip(4)))
-                cands.append(("v8", lambda: run_hip(8)))      # 128 x 128 tiles (short M / N grids)
+                cands += [_CAND["v4"], _CAND["v8"]]      # v8: 128 x 128 tiles (short M / N grids)
                 if _underfilled(M, N):    # 64x128 / 128x64 tiles, 4- and 6-stage rings (batch-1 grids)
-                    cands += [(f"v{v}", (lambda v=v: run_hip(v))) for v in _SMALL_TILE]
+                    cands += _SMALL_CANDS
                     if K % 64 == 0 and K >= 128 and N % 160 == 0 and not gelu:   # 128 x 160 v6 tiles
-                        cands.append(("v6m128", lambda: run_hip(V6_M128)))
+                        cands.append(_CAND["v6m128"])
                     if K % 64 == 0 and K >= 128 and N % 80 == 0 and not gelu:    # 128 x 80, 4-wave v6
-                        cands.append(("v6w4", lambda: run_hip(V6_W4)))
+                        cands.append(_CAND["v6w4"])
                     if (a.stride(0) % 8 == 0 and (bias is None or bias.data_ptr() % 16 == 0)
                             and (r is None or r.data_ptr() % 16 == 0)):
-                        cands += _splitk_cands(M, N, K, epi, run_hip)
-            cands.append(("hip", lambda: run_hip(-1)))
-            if _LIB_GEMM and not gelu and dst is None:     # vendor GEMM only as an explicit opt-in
-                cands.append(("lib", run_lib))
-            choice = autotune.choose(("gemm", M, N, K, epi), cands, default="hip")
+                        cands += _splitk_cands(M, N, K, epi)
+            cands.append(("hip", -2))
+            lib = [("lib", run_lib)] if _LIB_GEMM and not gelu and dst is None else []   # vendor GEMM: explicit opt-in
+            choice = autotune.choose(("gemm", M, N, K, epi), _timed(cands, run_hip) + lib, default="hip")
         if choice == "lib" and (gelu or dst is not None):
             choice = "hip"
         if choice == "lib":
@@ -235,9 +291,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
         count("gemm", "hip")
         if act is not None:
             count("act_fused", "hip")
-        variant = choice if choice in _SPLITK else {"v7": 7, "v6": 6, "v5": 5, "v4": 4, "v8": 8, "w6": W6,
-                                                    "w6n160": W6_160, "v6m128": V6_M128, "v6w4": V6_W4,
-                                                    **_SMALL_NAMES}.get(choice, -2)
+        variant = dict(cands)[choice]
         y = run_hip(variant, final=True).view(*x.shape[:-1], N)
         if rs_part:
             # (no version counter: inference-mode tensors have none; the consumers take the partials only
@@ -285,6 +339,7 @@ def _linear_w8(x, weight, bias, residual):
         r = None if residual is None else residual.reshape(M, N).contiguous()
         b = None if bias is None else bias.to(torch.bfloat16).contiguous()
         out = torch.empty((M, N), device=x.device, dtype=x.dtype)
+        # (the one GEMM launch outside _gemm_launch: its own prototype, no variant and none of the optional operands)
         _check(_lib().cgs_gemm_bf16_w8(a.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(b), _ptr(r), M, N, K,
                                        a.stride(0), K, N, N if r is not None else 0, epi, 1.0, _stream()),
                "cgs_gemm_bf16_w8")
@@ -311,35 +366,25 @@ def linear_geglu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | Non
 
         def run_hip(variant):
             out = torch.empty((M, N2 // 2), device=x.device, dtype=x.dtype)
-            ws = _v7_ws(M, N2, K, x.device) if variant == 7 else None
-            if ws is not None:
-                _check(_lib().cgs_gemm_bf16_v7ws(a.data_ptr(), weight.data_ptr(), out.data_ptr(), _ptr(bias), None,
-                                                 M, N2, K, K, K, N2 // 2, 0, epi, 1.0, ws.data_ptr(), ws.numel(),
-                                                 _stream()), "cgs_gemm_bf16_v7ws")
-                return out
-            _check(_lib().cgs_gemm_bf16_v(a.data_ptr(), weight.data_ptr(), out.data_ptr(), _ptr(bias), None,
-                                          M, N2, K, K, K, N2 // 2, 0, epi, 1.0, variant, _stream()),
-                   "cgs_gemm_bf16")
-            return out
+            return _gemm_launch(a, weight, out, bias, None, M, N2, K, epi, variant, ldc=N2 // 2)
 
-        choice = "hip"
+        choice, cands = "hip", [("hip", -2)]      # -2: the process-wide choice (auto unless set)
         if M * N2 * K >= (1 << 27) and K % 32 == 0:
             cands = []
             if K % 64 == 0:
                 if K >= 128:
-                    cands.append(("v7", lambda: run_hip(7)))
+                    cands.append(_CAND["v7"])
                     if N2 % 160 == 0:    # 256x160 tiles with the GEGLU epilogue (pq::run GG)
-                        cands.append(("v6", lambda: run_hip(6)))
-                cands.append(("v5", lambda: run_hip(5)))
+                        cands.append(_CAND["v6"])
+                cands.append(_CAND["v5"])
             if _w6_ok(M, N2, K, epi):
-                cands.append(("w6", lambda: run_hip(W6)))
-            cands.append(("v4", lambda: run_hip(4)))
+                cands.append(_CAND["w6"])
+            cands.append(_CAND["v4"])
             if _underfilled(M, N2):
-                cands += [("v8", lambda: run_hip(8))] + [(f"v{v}", (lambda v=v: run_hip(v))) for v in _SMALL_TILE]
-            cands.append(("hip", lambda: run_hip(-1)))
-            choice = autotune.choose(("gemm_geglu", M, N2, K, epi), cands, default="hip")
-        variant = {"v7": 7, "v6": 6, "v5": 5, "v4": 4, "v8": 8, "w6": W6, **_SMALL_NAMES}.get(choice, -2)
-        return run_hip(variant).view(*x.shape[:-1], N2 // 2)
+                cands += [_CAND["v8"]] + _SMALL_CANDS
+            cands.append(("hip", -2))
+            choice = autotune.choose(("gemm_geglu", M, N2, K, epi), _timed(cands, run_hip), default="hip")
+        return run_hip(dict(cands)[choice]).view(*x.shape[:-1], N2 // 2)
     count("gemm_geglu", be)
     # reference path expects the *interleaved* weight too, undo it
     w = geglu_deinterleave(weight)
@@ -721,7 +766,6 @@ def tome_match(a: torch.Tensor, b: torch.Tensor):
     return (an @ bn.transpose(-1, -2)).max(dim=-1)
 
 
-EPI_F32OUT = 16
 # K22: one-head D=512 attention (KL-VAE mid block) through materialised scores (CGS_WIDE_ATTN=flash
 # keeps the flash kernel). S chunks are capped at 2^28 elements (1 GiB fp32).
 _WIDE_MAT = os.environ.get("CGS_WIDE_ATTN", "mat") != "flash"
@@ -754,15 +798,11 @@ def _attention_wide_mat(q, k, v):
         for r0 in range(0, Sq, chunk):
             m = min(chunk, Sq - r0)
             qa = q.data_ptr() + 2 * (b * q.stride(0) + r0 * q.stride(1))
-            ws = _v7_ws(m, Sk, D, dev)
-            _check(lib.cgs_gemm_bf16_v7ws(qa, k[b].data_ptr(), s.data_ptr(), None, None, m, Sk, D, q.stride(1),
-                                          k.stride(1), Sk, 0, EPI_F32OUT, alpha, _ptr(ws),
-                                          0 if ws is None else ws.numel(), st), "cgs_gemm_bf16_v7ws(f32)")
+            _gemm_launch(qa, k[b], s, None, None, m, Sk, D, EPI_F32OUT, 7, lda=q.stride(1), ldw=k.stride(1),
+                         alpha=alpha, v7ws=True, device=dev, label="cgs_gemm_bf16_v7ws(f32)")
             _check(lib.cgs_softmax2_f32_bf16(s.data_ptr(), p.data_ptr(), m, Sk, Sk, Sk, st), "cgs_softmax2_f32_bf16")
-            ws = _v7_ws(m, D, Sk, dev)
             oa = o.data_ptr() + 2 * (b * o.stride(0) + r0 * o.stride(1))
-            _check(lib.cgs_gemm_bf16_v7ws(p.data_ptr(), vt.data_ptr(), oa, None, None, m, D, Sk, Sk, Sk, D, 0, 0, 1.0,
-                                          _ptr(ws), 0 if ws is None else ws.numel(), st), "cgs_gemm_bf16_v7ws")
+            _gemm_launch(p, vt, oa, None, None, m, D, Sk, 0, 7, v7ws=True, device=dev)
     return o
 
 
@@ -2171,99 +2211,66 @@ def _gelu_gns_ok(M, N, K, hw) -> bool:
             and N % 8 == 0 and K % 64 == 0 and K >= 128 and _native.has_kernel("cgs_gemm_bf16_gelu_gns"))
 
 
-def _gelu_gns(a, w, b, rs, cs, M, N, K, epi, hw, device, dtype):
-    """The v6 GELU (+ LN-fold) GEMM whose epilogue also writes per-(image, 64-row block, column) sums of squares
-    partials of its output (returned with it; the caller attaches them to its final view as
-    ``y._cgs_grnpart``): the GlobalResponseNorm over y (``grn_nhwc`` / ``grn_fold_weight``) then takes its
-    statistics from them instead of a pass over y."""
-    out = torch.empty((M, N), device=device, dtype=dtype)
-    part = torch.empty((M // 64) * N, device=device, dtype=torch.float32)
-    _check(_lib().cgs_gemm_bf16_gelu_gns(a.data_ptr(), w.data_ptr(), out.data_ptr(), b.data_ptr(), _ptr(rs), _ptr(cs),
-                                         M, N, K, a.stride(0), K, N, epi, part.data_ptr(), hw, _stream()),
-           "cgs_gemm_bf16_gelu_gns")
-    return out, part
-
-
 def linear_lnfold(x: torch.Tensor, rs: torch.Tensor, w2: torch.Tensor, cs: torch.Tensor, b2: torch.Tensor,
                   geglu: bool = False, act: str | None = None, gns_hw: int | None = None) -> torch.Tensor:
     """``LN(x) @ W^T + b`` (or the GEGLU of it, with interleaved W' rows) from the raw rows ``x``, the
     row statistics ``rs`` and ``lnfold_weights`` -- the LayerNorm never materialises (K07 folded
     into the GEMM epilogue of the v7 kernel). ``act="gelu"``: GELU of it (Cascade's LayerNorm ->
     ChannelMLP Linear -> GELU), on the v6 ACT / mc::tile kernels. ``gns_hw`` (rows per image): when the
-    v6 kernel runs, its epilogue also leaves the GRN statistics partials of the output (``_gelu_gns``)."""
+    v6 kernel runs, its epilogue also writes per-(image, 64-row block, column) sums of squares partials of its
+    output, attached as ``y._cgs_grnpart``: the GlobalResponseNorm over y (``grn_nhwc`` / ``grn_fold_weight``)
+    then takes its statistics from them instead of a pass over y."""
     K = x.shape[-1]
     a = x.reshape(-1, K)
     if not a.is_contiguous():
         a = a.contiguous()
     M, N = a.shape[0], w2.shape[0]
     nout = N // 2 if geglu else N
-    epi = EPI_BIAS | (EPI_GEGLU if geglu else 0)
+    epi = EPI_BIAS | (EPI_GEGLU if geglu else 0) | (EPI_GELU if act == "gelu" else 0)
+    key = ("gemm_lnfold", M, N, K, epi)
     count("gemm_geglu" if geglu else "gemm", "hip")
-    if act == "gelu":
-        assert not geglu
-        epi |= EPI_GELU
-
-        def run_g(variant):
-            out = torch.empty((M, N), device=x.device, dtype=x.dtype)
-            _check(_lib().cgs_gemm_bf16_lnfold_v(a.data_ptr(), w2.data_ptr(), out.data_ptr(), b2.data_ptr(),
-                                                 rs.data_ptr(), cs.data_ptr(), M, N, K, K, K, N, epi, None, 0,
-                                                 variant, _stream()), "cgs_gemm_bf16_lnfold_v")
-            return out
-        cands = [("v8", lambda: run_g(8)), ("v6", lambda: run_g(6))]
-        if _underfilled(M, N):
-            cands += [(f"v{v}", (lambda v=v: run_g(v))) for v in _SMALL_TILE]
-        choice = autotune.choose(("gemm_lnfold", M, N, K, epi), cands, default="v6" if N % 160 == 0 else "v8")
-        if choice == "v6" and _gelu_gns_ok(M, N, K, gns_hw):
-            y, part = _gelu_gns(a, w2, b2, rs, cs, M, N, K, epi | EPI_LNFOLD, gns_hw, x.device, x.dtype)
-            y = y.view(*x.shape[:-1], N)
-            y._cgs_grnpart = (part, y.data_ptr(), gns_hw)
-            return y
-        return run_g({"v6": 6, "v8": 8, **_SMALL_NAMES}.get(choice, -1)).view(*x.shape[:-1], N)
 
     def run(variant):
         out = torch.empty((M, nout), device=x.device, dtype=x.dtype)
         if isinstance(variant, str):                           # split-K (batch-1 grids)
             return _splitk_run(a, w2, out, b2, None, rs, cs, M, N, K, epi | EPI_LNFOLD, variant)
-        ws = _v7_ws(M, N, K, x.device) if variant in (-1, 7) else None
-        _check(_lib().cgs_gemm_bf16_lnfold_v(a.data_ptr(), w2.data_ptr(), out.data_ptr(), b2.data_ptr(), rs.data_ptr(),
-                                             cs.data_ptr(), M, N, K, K, K, nout, epi, _ptr(ws),
-                                             0 if ws is None else ws.numel(), variant, _stream()),
-               "cgs_gemm_bf16_lnfold_v")
-        return out
+        return _gemm_launch(a, w2, out, b2, None, M, N, K, epi, variant, ldc=nout, rs=rs, cs=cs)
 
-    variant = -1                  # v6 / v7 by shape
-    w6 = _w6_cands(M, N, K, epi | EPI_LNFOLD, run)
-    if _underfilled(M, N) and _native.has_kernel("cgs_gemm_bf16_lnfold_v"):
-        cands = [("v7", lambda: run(-1)), ("v8", lambda: run(8))] + [(f"v{v}", (lambda v=v: run(v))) for v in _SMALL_TILE]
-        if N % 160 == 0:    # 256x160 tiles (plain or GEGLU): whole rounds where 256x256 leaves a partial one
-            cands.append(("v6", lambda: run(6)))
-            if not geglu:   # 128 x 160 tiles, and 128 x 80 with one wave group
-                cands += [("v6m128", lambda: run(V6_M128)), ("v6w4", lambda: run(V6_W4))]
-        if not geglu:
-            cands += _splitk_cands(M, N, K, epi | EPI_LNFOLD, run)
-        choice = autotune.choose(("gemm_lnfold", M, N, K, epi), cands + w6, default="v7")
-        variant = choice if choice in _SPLITK else {"v8": 8, "v6": 6, "w6": W6, "w6n160": W6_160,
-                                                    "v6m128": V6_M128, "v6w4": V6_W4,
-                                                    **_SMALL_NAMES}.get(choice, -1)
-    elif geglu and N % 160 == 0 and _native.has_kernel("cgs_gemm_bf16_lnfold_v"):
-        choice = autotune.choose(("gemm_lnfold", M, N, K, epi),
-                                 [("v7", lambda: run(7)), ("v6", lambda: run(6))] + w6, default="v7")
-        variant = {"v6": 6, "w6": W6, "w6n160": W6_160}.get(choice, 7)
-    elif not geglu and N % 160 == 0 and N > 1280 and _native.has_kernel("cgs_gemm_bf16_lnfold_v"):
-        # wide non-GEGLU projections (fused QKV): 256x160 tiles give whole rounds where 256x256 leave
-        # a partial last round (N = 1920 / 3840 at M = 65536 / 16384) -- measured per shape
-        choice = autotune.choose(("gemm_lnfold", M, N, K, epi),
-                                 [("v7", lambda: run(7)), ("v6", lambda: run(6))] + w6, default="v7")
-        variant = {"v6": 6, "w6": W6, "w6n160": W6_160}.get(choice, 7)
-    elif w6 and _native.has_kernel("cgs_gemm_bf16_lnfold_v"):
-        choice = autotune.choose(("gemm_lnfold", M, N, K, epi), [("v7", lambda: run(-1))] + w6, default="v7")
-        variant = {"w6": W6, "w6n160": W6_160}.get(choice, -1)
+    if act == "gelu":
+        assert not geglu
+        cands = [_CAND["v8"], _CAND["v6"]]
+        if _underfilled(M, N):
+            cands += _SMALL_CANDS
+        choice = autotune.choose(key, _timed(cands, run), default="v6" if N % 160 == 0 else "v8")
+        if choice == "v6" and _gelu_gns_ok(M, N, K, gns_hw):
+            out = torch.empty((M, N), device=x.device, dtype=x.dtype)
+            part = torch.empty((M // 64) * N, device=x.device, dtype=torch.float32)
+            _gemm_launch(a, w2, out, b2, None, M, N, K, epi | EPI_LNFOLD, 6, rs=rs, cs=cs, part=part, hw=gns_hw)
+            y = out.view(*x.shape[:-1], N)
+            y._cgs_grnpart = (part, y.data_ptr(), gns_hw)
+            return y
+        return run(dict(cands)[choice]).view(*x.shape[:-1], N)
+
+    cands = None                  # no tuning: -1, v6 / v7 by shape
+    w6 = _w6_cands(M, N, K, epi | EPI_LNFOLD)
+    if _native.has_kernel("cgs_gemm_bf16_lnfold_v"):
+        if _underfilled(M, N):    # here and with w6 alone "v7" is the entry's own choice (-1)
+            cands = [("v7", -1), _CAND["v8"]] + _SMALL_CANDS
+            if N % 160 == 0:    # 256x160 tiles (plain or GEGLU): whole rounds where 256x256 leaves a partial one
+                cands.append(_CAND["v6"])
+                if not geglu:   # 128 x 160 tiles, and 128 x 80 with one wave group
+                    cands += [_CAND["v6m128"], _CAND["v6w4"]]
+            if not geglu:
+                cands += _splitk_cands(M, N, K, epi | EPI_LNFOLD)
+            cands += w6
+        elif N % 160 == 0 and (geglu or N > 1280):
+            # GEGLU, and wide non-GEGLU projections (fused QKV): 256x160 tiles give whole rounds where 256x256
+            # leave a partial last round (N = 1920 / 3840 at M = 65536 / 16384) -- measured per shape
+            cands = [_CAND["v7"], _CAND["v6"]] + w6
+        elif w6:
+            cands = [("v7", -1)] + w6
+    variant = dict(cands)[autotune.choose(key, _timed(cands, run), default="v7")] if cands else -1
     return run(variant).view(*x.shape[:-1], nout)
-
-
-W6, W6_160 = 16, 17      # gemm_w6.hip (256 / 160-wide tiles) through cgs_gemm_bf16_v / _lnfold_v
-V6_M128 = 19             # v6 with 128 x 160 tiles (pq::run NI = 2): the short-M grids
-V6_W4 = 20               # v6 with 128 x 80 tiles, 4 waves, two workgroups per CU (pq::run NW = 4): batch-1 grids
 
 
 def _w6_ok(M, N, K, epi, bn=256) -> bool:
@@ -2274,49 +2281,35 @@ def _w6_ok(M, N, K, epi, bn=256) -> bool:
     return bool(_lib().cgs_gemm_w6_ok(M, N, K, K, K, nout, nout if epi & EPI_RESIDUAL else 0, epi, bn))
 
 
-def _w6_cands(M, N, K, epi, run):
-    """("w6", ...) / ("w6n160", ...) autotune candidates where the shape is in their domain."""
-    out = []
-    if _w6_ok(M, N, K, epi):
-        out.append(("w6", lambda: run(W6)))
+def _w6_cands(M, N, K, epi, run=None):
+    """("w6", variant) / ("w6n160", variant) autotune candidates where the shape is in their domain (``run``: unused,
+    the callables come from ``_timed``)."""
+    out = [_CAND["w6"]] if _w6_ok(M, N, K, epi) else []
     if N % 160 == 0 and _w6_ok(M, N, K, epi, 160):
-        out.append(("w6n160", lambda: run(W6_160)))
+        out.append(_CAND["w6n160"])
     return out
 
 
-_CUS: list = []
-# small-tile GEMM variants (gemm.hip gemm_v8_launch): 10 / 11 = 64x128 / 128x64 with a 4-stage ring,
-# 12 / 13 = the same with 6 stages, 14 = 128x128 with 5 stages
-_SMALL_TILE = (10, 11, 12, 13, 14)
-_SMALL_NAMES = {f"v{v}": v for v in _SMALL_TILE}
-# split-K forms of the v8 family (cgs_gemm_bf16_splitk): autotune name -> (tile variant, slices)
-_SPLITK = {"sk2v8": (8, 2), "sk4v8": (8, 4), "sk2v10": (10, 2), "sk4v10": (10, 4), "sk2v11": (11, 2),
-           "sk4v11": (11, 4), "sk8v8": (8, 8)}
-
-
-def _splitk_cands(M, N, K, epi, run):
+def _splitk_cands(M, N, K, epi, run=None):
     """Split-K autotune candidates for an under-filled grid (batch-1 shapes: a 128 x 128 grid under two
     workgroups per CU): the K slices multiply the workgroup count, one reduce pass applies the epilogue.
     Candidates by default from K = 4096 (CGS_SPLITK=1: every K, 0: never): slower than the best single-pass
     tile on every SDXL batch-1 shape (profiles/r05/splitk.md -- the fp32 partial round trip costs more than
     the fuller grid gains at K <= 5120), -3.3 % per Cascade batch-1 job on Stage C's K = 8192 ChannelMLP
-    projection (profiles/r05/splitk_cascade.md)."""
+    projection (profiles/r05/splitk_cascade.md). (name, name) pairs: a split-K candidate's variant is its
+    ``_SPLITK`` name (``run``: unused, as in ``_w6_cands``)."""
     mode = os.environ.get("CGS_SPLITK", "auto")
     if (epi & ~(EPI_BIAS | EPI_RESIDUAL | EPI_LNFOLD | EPI_GELU)) or N % 8 or not _underfilled(M, N) \
             or not _native.has_kernel("cgs_gemm_bf16_splitk") or mode == "0" or (mode != "1" and K < 4096):
         return []
-    return [(name, (lambda name=name: run(name))) for name, (_, s) in _SPLITK.items()
-            if K % (32 * s) == 0 and K // s >= 256]
+    return [(name, name) for name, (_, s) in _SPLITK.items() if K % (32 * s) == 0 and K // s >= 256]
 
 
 def _splitk_run(a, w, o, bias, r, rs, cs, M, N, K, epi, name):
-    variant, s = _SPLITK[name]
-    ws = torch.empty(s * M * N, device=a.device, dtype=torch.float32)
-    _check(_lib().cgs_gemm_bf16_splitk(a.data_ptr(), w.data_ptr(), o.data_ptr(), _ptr(bias), _ptr(r), _ptr(rs),
-                                       _ptr(cs), M, N, K, a.stride(0), w.stride(0), N, N if r is not None else 0,
-                                       epi, 1.0, s, variant, ws.data_ptr(), ws.numel() * 4, _stream()),
-           "cgs_gemm_bf16_splitk")
-    return o
+    return _gemm_launch(a, w, o, bias, r, M, N, K, epi, name, lda=a.stride(0), ldw=w.stride(0), rs=rs, cs=cs)
+
+
+_CUS: list = []
 
 
 def _num_cus() -> int:
@@ -2568,7 +2561,7 @@ def grn_nhwc(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pre_gelu:
 
 
 def _grn_part(x, N, HW, C):
-    """The GNS partials attached by ``_gelu_gns`` when they describe exactly this tensor, else None."""
+    """The GNS partials attached by ``linear_lnfold`` when they describe exactly this tensor, else None."""
     h = getattr(x, "_cgs_grnpart", None)
     if (h is None or h[1] != x.data_ptr() or h[2] != HW or not x.is_contiguous() or x.dtype != torch.bfloat16
             or h[0].numel() != N * (HW // 64) * C or N > 64 or C % 8):

@@ -105,9 +105,7 @@ def gemm_rows(args, dev):
             for cand, v in (("hip", -1), ("v6", 6), ("v4", 4), ("v8", 8)):
                 if m <= 128 and v != -1:
                     continue
-                fn = lambda v=v: core._check(core._lib().cgs_gemm_bf16_v(           # noqa: E731
-                    a.data_ptr(), w.data_ptr(), out.data_ptr(), b.data_ptr(), None, m, n, k, k, k, n, 0, epi, 1.0, v,
-                    core._stream()), "cgs_gemm_bf16_v")
+                fn = lambda v=v: core._gemm_launch(a, w, out, b, None, m, n, k, epi, v)           # noqa: E731
                 row[cand] = timed(fn, args.iters, args.reps)
             run = lambda: ops.linear(a, w, b, act=act)              # noqa: E731
             run()
