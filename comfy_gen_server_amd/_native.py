@@ -208,6 +208,11 @@ KERNEL_SIGNATURES = {
     "cgs_flash_attn_fwd_ks": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _F, _I, _P, _P, _P],
     "cgs_flash_attn_fwd_kv2": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _P],
     "cgs_conv2d_nhwc_gns": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    # ... + variant (6, or 22: the patch form, partial blocks in patch order)
+    "cgs_conv2d_nhwc_gns_v": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
+    # timing probe: the v6 conv with the A DMAs of one tap only (wrong results by design): x, w, bias, res, out,
+    # N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo
+    "cgs_conv2d_nhwc_probe": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     # row-sharded GroupNorm (parallel/spatial.py): band statistics, then apply with combined (mean, rstd)
     "cgs_groupnorm_band_stats": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "cgs_groupnorm_apply_stats": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -19,6 +19,7 @@
 #include "mfma_core.h"
 #include "mfma_pp.h"
 #include "mfma_pp160.h"
+#include "mfma_pp160p.h"
 #include "mfma_ppk.h"
 
 #define EPI_BIAS 1
@@ -520,6 +521,17 @@ struct ConvGatherKD {
   }
 };
 
+// Timing probe only (cgs_conv2d_nhwc_probe, never dispatched): ConvGatherKD that issues the A DMAs of tap 0 and skips
+// the other taps' -- the B DMAs and every MFMA stay, the results are wrong by design. What the v6 conv would gain
+// at most from not fetching its A rows once per tap (the patch form, mfma_pp160p.h).
+struct ConvGatherKD1 : ConvGatherKD {
+  static constexpr bool kTapProbe = true;
+  __device__ __forceinline__ bool has_a(int k0) const { return k0 < a->Cin; }
+  __device__ __forceinline__ void dma(int s, int k0, unsigned char* dst) const {
+    if (has_a(k0)) ConvGatherKD::dma(s, k0, dst);
+  }
+};
+
 // ConvGatherKD for the nearest-2x-upsampled input (CONV_UP2X, single input): the source pixel of tap (ky, kx)
 // is ((py + ky) >> 1, (px + kx) >> 1) -- not an affine function of the tap, so the lane keeps its top-left
 // (py, px) in upsampled coordinates and its image's base offset, and does two adds, two shifts and two
@@ -722,12 +734,14 @@ static void with_loader(int ld, F f) {
 }
 
 // LD: 0 ConvGatherA8 (generic: UP2X, big filters), 1 ConvGatherK (64-bit offsets: an input >= 2 GiB),
-// 2 ConvGatherKD (buffer_load ... lds, the default where it applies), 3 ConvGatherKU (its upsample-aware form)
+// 2 ConvGatherKD (buffer_load ... lds, the default where it applies), 3 ConvGatherKU (its upsample-aware form),
+// 4 ConvGatherKD1 (the one-tap timing probe)
 template <int LD>
 using ConvLoaderFor = typename std::conditional<
+    LD == 4, ConvGatherKD1, typename std::conditional<
     LD == 3, ConvGatherKU,
     typename std::conditional<LD == 2, ConvGatherKD,
-                              typename std::conditional<LD == 1, ConvGatherK<true>, ConvGatherA8>::type>::type>::type;
+                              typename std::conditional<LD == 1, ConvGatherK<true>, ConvGatherA8>::type>::type>::type>::type;
 // NJ: 16-column MFMA tiles per wave group -- 5 (256 x 160 tiles) or 4 (256 x 128: Cout = 128 / 256 / 384 ...,
 // variant 18)
 template <int LD, int DS = 0, bool GNS = false, int NJ = 5, int PFE = CGS_CONV_PFE>
@@ -804,6 +818,35 @@ static void conv_v6_go(ConvArgs& a, hipStream_t stream, bool n128 = false) {
       default: conv_v6_launch<L, 51>(a, grid, stream);
     }
   });
+}
+
+// v6p (variant 22): the patch form of v6 for the 3 x 3 / stride 1 / pad 1 conv (mfma_pp160p.h) -- a tile is one
+// 16 x 16 output patch, its 18 x 18 input patch is staged once per 64-channel slab and the nine taps read it shifted.
+template <bool GNS>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_nhwc_v6p_kernel(ConvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  mc::Epi e = conv_epi(a);
+  e.gnp = a.gnp;
+  e.hw = a.H * a.W;
+  pq::run_patch<GNS>(a.in, a.N, a.H, a.W, a.Cin, a.w, a.Cout, e, smem, a.tiles_n);
+}
+
+// The v6p domain: bf16 3 x 3 / stride 1 / pad 1, one source, no upsample, no activation, Cin % 64 == 0,
+// Cout % 8 == 0, every image under 2 GiB (per-image descriptors); the GroupNorm-partials epilogue needs whole patches.
+static bool conv_patch_ok(const ConvArgs& a) {
+  const long long units = (long long)a.N * ((a.H + 15) / 16) * ((a.W + 15) / 16) * ((a.Cout + pq::BN - 1) / pq::BN);
+  return a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 && !a.in2 && !(a.flags & CONV_UP2X) && !a.act &&
+         a.Cin % 64 == 0 && a.Cout % 8 == 0 && a.Ho == a.H && a.Wo == a.W && (uintptr_t)a.bias % 8 == 0 &&
+         (long long)a.H * a.W * a.Cin * 2 < (1ll << 31) && units < (1ll << 31) &&
+         (!a.gnp || (a.H % 16 == 0 && a.W % 16 == 0));
+}
+
+static void conv_v6p_go(ConvArgs& a, hipStream_t stream) {
+  a.tiles_n = (a.Cout + pq::BN - 1) / pq::BN;
+  const long long T = (long long)a.N * ((a.H + 15) / 16) * ((a.W + 15) / 16) * a.tiles_n;
+  const long long grid = T < num_cus() ? T : num_cus();
+  if (a.gnp) conv_run<conv_nhwc_v6p_kernel<true>>(a, grid, pq::THREADS, pq::P_LDS, stream);
+  else conv_run<conv_nhwc_v6p_kernel<false>>(a, grid, pq::THREADS, pq::P_LDS, stream);
 }
 
 // v7: the persistent 256 x 256 ping-pong with cross-tile prefetch and register epilogue (mfma_ppk.h)
@@ -1101,6 +1144,11 @@ static int conv_smalln_launch(const ConvArgs& a, hipStream_t stream) {
 // 256-row v2 tile for A/B comparisons.
 static int conv_launch(ConvArgs& a, hipStream_t stream, int variant = -2, void* ws = nullptr, long long ws_bytes = 0) {
   if (variant == -2) variant = g_conv_variant;
+  if (variant == 22) {   // the patch form: its domain or nothing (the caller keeps its other choice)
+    if (!conv_patch_ok(a)) return (int)hipErrorInvalidValue;
+    conv_v6p_go(a, stream);
+    return (int)hipGetLastError();
+  }
   if (a.Cout <= 16 && (variant != 2 || a.Cin % 64 || (a.in2 && a.C1 % 64))) return conv_smalln_launch(a, stream);
   // v3 needs Cout % 8 == 0 for the 16-B epilogue stores (SD/SDXL/VAE convs: all but the 3/4-channel
   // heads, which take v2).
@@ -1180,6 +1228,37 @@ CGS_EXPORT int cgs_conv2d_nhwc_gns(const void* x, const void* x2, int C1, const 
     return (int)hipErrorInvalidValue;
   a.gnp = gnp;
   conv_v6_go(a, stream);
+  return (int)hipGetLastError();
+}
+
+// cgs_conv2d_nhwc_gns on a chosen variant: 6 as above, 22 the patch form (H % 16 == 0, W % 16 == 0; the block of
+// gnp is then patch * 4 + wave row: the 64 pixels of four patch rows, each block written once).
+CGS_EXPORT int cgs_conv2d_nhwc_gns_v(const void* x, const void* x2, int C1, const void* w, const void* bias,
+                                     const void* res, void* out, int N, int H, int W, int Cin, int Cout, int kh, int kw,
+                                     int stride, int pad, int Ho, int Wo, int flags, float* gnp, int variant,
+                                     hipStream_t stream) {
+  if (variant != 22)
+    return variant == 6 ? cgs_conv2d_nhwc_gns(x, x2, C1, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad,
+                                              Ho, Wo, flags, gnp, stream)
+                        : (int)hipErrorInvalidValue;
+  ConvArgs a = conv_args(x, x2, C1, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, flags);
+  if (!gnp || ((uintptr_t)gnp % 16) || !conv_shape_ok(a)) return (int)hipErrorInvalidValue;
+  a.gnp = gnp;
+  if (!conv_patch_ok(a)) return (int)hipErrorInvalidValue;
+  conv_v6p_go(a, stream);
+  return (int)hipGetLastError();
+}
+
+// Timing probe (tools/probes/conv_patch_ceiling.py): the v6 conv with the A DMAs of tap 0 only (ConvGatherKD1).
+// The output is wrong by design; nothing dispatches here.
+CGS_EXPORT int cgs_conv2d_nhwc_probe(const void* x, const void* w, const void* bias, const void* res, void* out, int N,
+                                     int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int Ho,
+                                     int Wo, hipStream_t stream) {
+  ConvArgs a = conv_args(x, nullptr, Cin, w, bias, res, out, N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, 0);
+  if (!conv_shape_ok(a) || Cout % 8 || Cout <= 16 || !conv_variant_ok(a, 6) || conv_pq_loader(a) != 2)
+    return (int)hipErrorInvalidValue;
+  const long long T = conv_tiles(a, pq::BM, pq::BN);
+  conv_v6_launch<4, 51>(a, (int)(T < num_cus() ? T : num_cus()), stream);
   return (int)hipGetLastError();
 }
 

@@ -39,6 +39,12 @@ __device__ __forceinline__ void untracked_load(u32x2v& d, const void* p) {
 
 constexpr int BM = 256, BN = 160, BK = 64;
 constexpr int THREADS = 512;
+// A timing-probe loader (``static constexpr bool kTapProbe``; ``has_a(k0)``: whether it issues its A DMAs for the
+// K-tile at k0) -- conv.hip ConvGatherKD1: run() sizes its counted waits by what was really issued.
+template <class T, class = void>
+struct tap_probe : std::false_type {};
+template <class T>
+struct tap_probe<T, std::void_t<decltype(T::kTapProbe)>> : std::true_type {};
 constexpr int A_BYTES = BM * 128;
 constexpr int B_BYTES = BN * 128;
 constexpr int STAGE = A_BYTES + B_BYTES;
@@ -220,7 +226,15 @@ __device__ __forceinline__ void run(AL& al, const u16* __restrict__ W, long long
     stage_part(0, kt, slot);
     if constexpr ((DS & 3) != 0) stage_part(1, kt, slot);
   };
-  auto wait_tile = [&]() {   // all but one K-tile's DMAs (BN = 160: 7 in group 0, 6 in group 1) retired
+  // kin: the K-tile left in flight (read by a tap_probe loader only, whose A DMAs exist for some K-tiles only)
+  auto wait_tile = [&](int kin) {   // all but one K-tile's DMAs (BN = 160: 7 in group 0, 6 in group 1) retired
+    if constexpr (tap_probe<AL>::value) {
+      if (!al.has_a(kin * BK)) {
+        if (!Gm::B_HALF || wave < Gm::REM / 8) mc::wait_vmcnt<Gm::NBG>();
+        else mc::wait_vmcnt<Gm::NBG - 1>();
+        return;
+      }
+    }
     if (!Gm::B_HALF || wave < Gm::REM / 8) mc::wait_vmcnt<Gm::NA + Gm::NBG>();
     else mc::wait_vmcnt<Gm::NA + Gm::NBG - 1>();
   };
@@ -578,7 +592,7 @@ __device__ __forceinline__ void run(AL& al, const u16* __restrict__ W, long long
   setup(m0, n0);
   stage(0, 0);
   stage(nk > 1 ? 1 : 0, 1);
-  wait_tile();
+  wait_tile(nk > 1 ? 1 : 0);
   pp::barrier();
   if (NW == 8 && grp == 1) pp::barrier();   // stagger: group 1 runs one segment behind group 0
 
@@ -615,7 +629,7 @@ __device__ __forceinline__ void run(AL& al, const u16* __restrict__ W, long long
       if constexpr ((DS & 4) != 0) stage_part(1, kst, slot2);
       read_frags(S, 1);
       if constexpr ((DS & 4) == 0) stage_part(1, kst, slot2);
-      wait_tile();
+      wait_tile(kst);
       if (PFE && PF) prefetch(m0, n0, hb, PFE == 1 && hr);
       pp::wait_lgkm0();
       pp::barrier();

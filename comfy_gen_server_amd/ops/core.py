@@ -1015,8 +1015,34 @@ def _upconv_use_taps(N, H, W, Cin, Cout, cached) -> bool:
     return cached and Cin >= 256 and Cout >= 32 and N * H * W * Cin * Cout * 36 >= (1 << 27)
 
 
+def _conv_patch_ok(x, x2, bias, Cin, Cout, kh, kw, stride, padding, upsample2x) -> bool:
+    """The domain of the patch form of the v6 conv (variant 22, csrc/kernels/mfma_pp160p.h; conv.hip conv_patch_ok):
+    bf16 3 x 3 / stride 1 / pad 1, one source, no upsample, Cin % 64 == 0, Cout % 8 == 0, every image under 2 GiB."""
+    H, W = x.shape[2], x.shape[3]
+    return (kh == 3 and kw == 3 and stride == 1 and padding == 1 and x2 is None and not upsample2x
+            and x.dtype == torch.bfloat16 and Cin % 64 == 0 and Cout % 8 == 0 and H * W * Cin * 2 < (1 << 31)
+            and (bias is None or bias.data_ptr() % 8 == 0) and _native.has_kernel("cgs_conv2d_nhwc_gns_v"))
+
+
+def _conv_use_patch(variant: int, N, H, W, Cin, Cout) -> bool:
+    """Whether a conv inside the patch form's domain takes it. ``CGS_CONV_PATCH=1`` forces it, ``0`` keeps the other
+    choice (A/B runs; read per call). Otherwise it replaces the v6 choice (6) where it measured faster than v6 by
+    more than twice v6's own spread (profiles/r12/conv_patch_ab.md): see ``_PATCH_SHAPES``."""
+    mode = os.environ.get("CGS_CONV_PATCH", "")
+    if mode in ("0", "1"):
+        return mode == "1"
+    return variant == 6 and (N, H, W, Cin, Cout) in _PATCH_SHAPES
+
+
+# (N, H, W, Cin, Cout) of the convs that moved from v6 to the patch form (profiles/r12/conv_patch_ab.md)
+_PATCH_SHAPES = frozenset(
+    [(16, 128, 128, c, 320) for c in (320, 640, 960)] + [(16, 64, 64, c, 640) for c in (320, 640, 960, 1280, 1920)]
+    + [(16, 32, 32, c, 1280) for c in (640, 1280, 1920, 2560)])
+
+
 # Autotune candidate name -> variant number of cgs_conv2d_nhwc_v / _act (conv.hip: conv_launch, conv_v3_launch)
-CONV_VARIANTS = {"v2": 2, "v3": 3, "v4": 4, "v5": 5, "v6": 6, "v7": 7, "v8": 8, "v6n128": 18, "v6w4": 21, "auto": -2}
+CONV_VARIANTS = {"v2": 2, "v3": 3, "v4": 4, "v5": 5, "v6": 6, "v7": 7, "v8": 8, "v6n128": 18, "v6w4": 21, "v6p": 22,
+                 "auto": -2}
 _FUSED_ACT_CONV = ("v3", "v4", "v8")     # the mc::tile convs: their epilogue carries the activation
 
 
@@ -1146,6 +1172,7 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
 
         variant = -2            # process-wide override (cgs_conv_set_variant), default auto
         M = N * Ho * Wo
+        patch_ok = _conv_patch_ok(xc, x2c, bias, Cin, Cout, kh, kw, stride, padding, upsample2x)
         # Cout <= 16 (UNet / VAE conv_out): the narrow-output kernel, no tuning (csrc conv_launch)
         if M * Cout * Cin * kh * kw >= (1 << 27) and Cout > 16:
             cands = [("v4", lambda: run(4))]
@@ -1158,9 +1185,15 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
                     cands.append(("v6n128", lambda: run(18)))   # 256 x 128 tiles (e.g. the VAE's Cout = 128)
                 if Cout % 80 == 0 and kh * kw * Cin >= 128 and M <= 32768:
                     cands.append(("v6w4", lambda: run(21)))      # 128 x 80 tiles, 4 waves (batch-1 grids)
+                if patch_ok:
+                    cands.append(("v6p", lambda: run(22)))       # 16 x 16 patches, the input patch staged once
             choice = autotune.choose(("conv", N, H, W, Cin, Cout, kh, stride, padding, flags, int(r is not None))
                                      + ((("dual", C1),) if x2c is not None else ()), cands, default="auto")
             variant = CONV_VARIANTS[choice]
+        if patch_ok and variant != 22 and _conv_use_patch(variant, N, H, W, Cin, Cout):
+            variant = 22
+        elif variant == 22 and os.environ.get("CGS_CONV_PATCH", "") == "0":
+            variant = 6
         if (upsample2x and single and r is None and not gn_stats and kh == 3 and kw == 3 and stride == 1
                 and padding == 1 and Cout % 8 == 0 and weight.dtype == x.dtype
                 and _native.has_kernel("cgs_upconv_taps_nhwc")):
@@ -1176,14 +1209,16 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
 
             if _upconv_use_taps(N, H, W, Cin, Cout, weight_taps is not None):
                 return run_taps()
-        if (gn_stats and variant == 6 and _GNS and (Ho * Wo) % 256 == 0 and Cin % 64 == 0 and C1 % 64 == 0
+        if (gn_stats and variant in (6, 22) and _GNS and (Ho * Wo) % 256 == 0 and Cin % 64 == 0 and C1 % 64 == 0
                 and Cout % 8 == 0 and kh * kw * Cin >= 128 and (bias is None or bias.data_ptr() % 8 == 0)
                 and _native.has_kernel("cgs_conv2d_nhwc_gns")):
             out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
             part = torch.empty(N * (Ho * Wo // 64) * Cout * 2, device=x.device, dtype=torch.float32)
-            _check(_lib().cgs_conv2d_nhwc_gns(*_conv_operands(xc, x2c, weight_nhwc, bias, r, out, kh, kw, stride,
-                                                              padding, flags), part.data_ptr(), _stream()),
-                   "cgs_conv2d_nhwc_gns")
+            pre = _conv_operands(xc, x2c, weight_nhwc, bias, r, out, kh, kw, stride, padding, flags)
+            if variant == 22 and H % 16 == 0 and W % 16 == 0:    # whole patches: block = patch * 4 + wave row
+                _check(_lib().cgs_conv2d_nhwc_gns_v(*pre, part.data_ptr(), 22, _stream()), "cgs_conv2d_nhwc_gns_v")
+            else:
+                _check(_lib().cgs_conv2d_nhwc_gns(*pre, part.data_ptr(), _stream()), "cgs_conv2d_nhwc_gns")
             out._cgs_gnpart = (part, out.data_ptr())
             return out
         return run(variant)
