@@ -40,7 +40,10 @@ __device__ __forceinline__ void philox10(uint32_t& c0, uint32_t& c1, uint32_t& c
   }
 }
 
-// 24-bit uniform strictly inside (0, 1): exact in fp32, identical on host and device.
+// 24-bit uniform in (0, 1], identical on host and device: k = v >> 8 gives (k + 0.5) 2^-24. From k = 2^23 on the sum
+// k + 0.5 needs 25 significand bits and is rounded to even (k odd: k + 1, k even: k), so k = 2^24 - 1 gives u = 1.0
+// and a normal of exactly 0; the smallest value is 2^-25 (k = 0). Host and device round alike. Keep the arithmetic:
+// every image generated so far depends on it.
 __device__ __forceinline__ float u01(uint32_t v) { return ((float)(v >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // 4 normals for element group g of the image with key `key` on `stream`.

@@ -1286,7 +1286,8 @@ def conv_transpose2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor |
 
 def upsample_nearest2x(x: torch.Tensor) -> torch.Tensor:
     be = backend_for("upsample", x, "cgs_upsample_nearest2x_nhwc")
-    if be == "hip" and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float16):
+    if be == "hip" and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float16) \
+            and x.shape[1] % 8 == 0:      # the kernel moves 16-byte chunks of 8 channels
         count("upsample", "hip")
         N, C, H, W = x.shape
         xc = x.contiguous(memory_format=torch.channels_last)
@@ -1351,7 +1352,8 @@ def depthwise_conv2d_nhwc_lnstats(x: torch.Tensor, w_kkc: torch.Tensor, bias: to
 # ----------------------------------------------------------------------------------------------
 def silu(x: torch.Tensor) -> torch.Tensor:
     be = backend_for("silu", x, "cgs_silu")
-    if be == "hip" and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous():
+    if be == "hip" and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous() \
+            and x.data_ptr() % 16 == 0:       # 16-byte vector loads: a view at an odd storage offset goes to ATen
         count("silu", "hip")
         y = torch.empty_like(x)
         _check(_lib().cgs_silu(x.data_ptr(), y.data_ptr(), x.numel(), _DT[x.dtype], _stream()), "cgs_silu")
@@ -1416,7 +1418,7 @@ def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0,
                        flip_sin_to_cos: bool = True) -> torch.Tensor:
     """Sinusoidal timestep embedding: [cos | sin] (util.py:229-249 semantics), fp32 out."""
     be = backend_for("timestep_embedding", t, "cgs_timestep_embedding")
-    if be == "hip" and dim % 2 == 0:
+    if be == "hip" and dim % 2 == 0 and t.shape[0] > 0 and dim > 0:   # an empty result: no launch of a zero-block grid
         count("timestep_embedding", "hip")
         tt = t.float().contiguous()
         out = torch.empty((t.shape[0], dim), device=t.device, dtype=torch.float32)
@@ -1434,10 +1436,17 @@ def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0,
     return emb
 
 
+def _f32_like(t: torch.Tensor, x: torch.Tensor) -> bool:
+    """``t`` can stand beside ``x`` in a flat fp32 kernel that indexes both by one offset: fp32, the same device,
+    the same shape (a broadcastable one has fewer elements) and contiguous."""
+    return t.dtype == torch.float32 and t.device == x.device and t.shape == x.shape and t.is_contiguous()
+
+
 def cfg_combine(cond: torch.Tensor, uncond: torch.Tensor, scale: float) -> torch.Tensor:
     """uncond + (cond - uncond) * scale (samplers.py:240), fused on device."""
     be = backend_for("cfg", cond, "cgs_cfg_combine")
-    if be == "hip" and cond.dtype == torch.float32 and cond.is_contiguous() and uncond.is_contiguous():
+    if be == "hip" and _f32_like(cond, cond) and _f32_like(uncond, cond):
+        count("cfg", "hip")
         out = torch.empty_like(cond)
         _check(_lib().cgs_cfg_combine(cond.data_ptr(), uncond.data_ptr(), out.data_ptr(), cond.numel(),
                                       float(scale), 0, _stream()), "cgs_cfg_combine")
@@ -1450,12 +1459,12 @@ def euler_step(x: torch.Tensor, denoised: torch.Tensor, noise: torch.Tensor | No
     """Fused Euler(-ancestral) update (sampling.py:148-164):
     d = (x - denoised)/sigma ; x = x + d*(sigma_down - sigma) ; x += noise*sigma_up."""
     be = backend_for("euler", x, "cgs_euler_step")
-    if be == "hip" and x.dtype == torch.float32 and denoised.dtype == torch.float32 and x.is_contiguous() \
-            and denoised.is_contiguous() and (noise is None or noise.is_contiguous()):
+    use_noise = noise is not None and sigma_up > 0
+    if be == "hip" and _f32_like(x, x) and _f32_like(denoised, x) and (not use_noise or _f32_like(noise, x)):
         count("euler", "hip")
         x = x.clone()  # the kernel updates in place; keep the caller's tensor intact
         _check(_lib().cgs_euler_step(x.data_ptr(), denoised.data_ptr(),
-                                     _ptr(noise) if (noise is not None and sigma_up > 0) else None,
+                                     _ptr(noise) if use_noise else None,
                                      x.numel(), float(sigma), float(sigma_down), float(sigma_up), _stream()),
                "cgs_euler_step")
         return x
@@ -1536,8 +1545,8 @@ def euler_ancestral_philox(x: torch.Tensor, denoised: torch.Tensor, sigma: float
     from ..sampling import rng
     be = backend_for("euler", x, "cgs_euler_ancestral_philox")
     index0, contiguous = rng.contiguous_inds(inds)
-    if be == "hip" and contiguous and x.dtype == torch.float32 and denoised.dtype == torch.float32 \
-            and x.is_contiguous() and denoised.is_contiguous() and _numel1(x.shape) % 4 == 0:
+    if be == "hip" and contiguous and _f32_like(x, x) and _f32_like(denoised, x) and _numel1(x.shape) % 4 == 0 \
+            and denoised.data_ptr() % 16 == 0:     # float4 loads of x (a fresh clone) and denoised
         count("euler", "hip")
         x = x.clone()
         _check(_lib().cgs_euler_ancestral_philox(x.data_ptr(), denoised.data_ptr(), int(x.shape[0]), _numel1(x.shape),

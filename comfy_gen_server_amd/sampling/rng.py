@@ -55,7 +55,17 @@ def _philox10(c0, c1, c2, c3, k0: torch.Tensor, k1: torch.Tensor):
     return c0, c1, c2, c3
 
 
+def seed_i64(seed: int) -> int:
+    """The 64-bit seed as the signed value with the same bit pattern: what a ``torch.int64`` tensor has to hold
+    for a kernel that reads it back as ``uint64_t`` to see ``seed & (2^64 - 1)``, bit 63 included."""
+    s = int(seed) & _M64
+    return s - (1 << 64) if s >= (1 << 63) else s
+
+
 def _u01(v: torch.Tensor) -> torch.Tensor:
+    """24-bit uniform in (0, 1]: (k + 0.5) 2^-24 with k = v >> 8, evaluated in fp32 as the kernel does. From
+    k = 2^23 on, k + 0.5 needs 25 significand bits and is rounded to even, so k = 2^24 - 1 gives exactly 1.0 (and a
+    normal of exactly 0); the smallest value is 2^-25. Host and device round alike: both see identical uniforms."""
     return ((v >> 8).to(torch.float32) + 0.5) * (1.0 / 16777216.0)
 
 

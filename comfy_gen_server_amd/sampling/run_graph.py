@@ -36,6 +36,7 @@ import torch
 
 from .. import ops
 from ..runtime import graphs
+from . import rng
 
 _lock = threading.Lock()
 stats: dict = {"capture": 0, "replay_runs": 0, "replay_steps": 0, "capture_failed": 0, "ineligible": {}}
@@ -242,7 +243,7 @@ def try_run(ksampler, guider, mk, x, sigmas, extra_args, callback):
         for dst, src in zip(plan.static, tensors):
             if dst is not src:
                 dst.copy_(src)
-    plan.key_t.copy_(torch.tensor([int(seed) & 0x7FFFFFFFFFFFFFFF, index0], dtype=torch.int64))
+    plan.key_t.copy_(torch.tensor([rng.seed_i64(seed), index0], dtype=torch.int64))
     for g, rec in zip(plan.graphs, plan.records + [None]):
         if g is not None:             # None: a segment that captured no work (nothing to replay)
             g.replay()
@@ -269,7 +270,7 @@ def _capture(ksampler, mk, x, sigmas, extra_args, tensors, seed, index0):
     """Capture the run with THIS job's tensors as the static inputs (the plan keeps them alive)."""
     p = _Plan()
     p.static = list(tensors)
-    p.key_t = torch.tensor([seed & 0x7FFFFFFFFFFFFFFF, index0], dtype=torch.int64, device=x.device)
+    p.key_t = torch.tensor([rng.seed_i64(seed), index0], dtype=torch.int64, device=x.device)
     p.graphs, p.records = [], []
     p.pool = torch.cuda.graph_pool_handle()
     side = torch.cuda.Stream(device=x.device)

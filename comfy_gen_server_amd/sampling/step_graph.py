@@ -215,7 +215,7 @@ def try_sample(mk, x, sigmas, extra_args, callback, kind: str, eta: float = 1.0,
             down, up = s[i + 1], 0.0
         rows.append((s[i], down, up, s_noise))
     plan.params[:n].copy_(torch.tensor(rows, dtype=torch.float32))
-    plan.meta.copy_(torch.tensor([0, int(extra_args["seed"]) & 0x7FFFFFFFFFFFFFFF, index0], dtype=torch.int64))
+    plan.meta.copy_(torch.tensor([0, rng.seed_i64(extra_args["seed"]), index0], dtype=torch.int64))
     plan.x.copy_(x)
     if plan.old is not None:
         plan.old.zero_()

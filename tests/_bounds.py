@@ -1,7 +1,8 @@
 """Per-element worst-case error bounds of the bf16 GEMM, conv and attention kernels (test_kernel_bounds_*.py) and
 of the bf16 / fp16 GroupNorm, LayerNorm, depthwise-conv and softmax2 kernels (test_norm_bounds_gpu.py), of the GRN
-family and of the planar image-space kernels (test_image_bounds_gpu.py), and of the fp32 GEMM, conv, norm and
-attention kernels (test_f32_bounds_gpu.py).
+family and of the planar image-space kernels (test_image_bounds_gpu.py), of the fp32 GEMM, conv, norm and
+attention kernels (test_f32_bounds_gpu.py), and of the small kernels of the sampler loop: CFG combine, Euler step,
+counter-based noise, the device-parameterised step, timestep embedding and SiLU (test_sampling_bounds_gpu.py).
 
 Every ``*_bound`` function takes the operands the kernel is given (CPU or GPU tensors of any float type), builds
 the result in fp64 and returns ``(ref, tol)``: two fp64 tensors of the output's shape. ``assert_within`` then
@@ -184,6 +185,49 @@ Attention (ops.f32.attention; attention_f32_bound), three launches a chunk of qu
           moves by at most 2 max ds, and so does the log of the normaliser)
   output  tol = store + C_ACC (Sk + 1) e (p |v|) + dp |v|     (K = Sk products of the stored p, alpha = 1)
   A row whose keys are all blocked is NaN on this path: ref = tol = nan, left out of assert_within and checked apart.
+
+The kernels of the sampling loop (csrc/kernels/rng.hip and the fp32 / 16-bit kernels at the head of elementwise.hip;
+test_sampling_bounds_cpu.py, test_sampling_bounds_gpu.py). Everything is fp32 arithmetic on fp32 data unless said
+otherwise; every scalar is the fp32 value the kernel is passed (_f32). No sum is longer than two terms, so C_ACC
+does not appear: every term is one counted rounding. Factors (1 + k e) absorb the second-order products. The device
+libm figures are supposed, like EXPF_REL and ERFF_REL: LOGF_REL = 2 ulp for logf, SINCOSF_REL = 2 ulp for sinf and
+cosf (1 ulp = 2 e); EXP2_REL for the v_exp_f32 inside __expf is the supposed figure of the softmax bounds.
+cfg_combine_bound, ref = u + (c - u) s: the difference, the product and the sum round once each; a contraction of
+  the last two into an fma only removes one.   tol = (2 e |c - u| |s| + e |ref|) (1 + 2e)
+euler_step_bound, D = (x - den) / sigma, dt = sigma_down - sigma, x1 = x + D dt, ref = x1 + noise sigma_up:
+  the host's 1.0f / sigma and sigma_down - sigma (a true division and a subtraction: e each), x - den and its product
+  with the reciprocal (e each): d dt is within 4 e |D dt| of D dt; fmaf(d, dt, x) rounds once, e |x1|;
+  fmaf(noise, sigma_up, x1) once more, e |ref|. The torch form of the same update (the fallback of ops.euler_step)
+  rounds the two products on their own: e |D dt| and e |noise sigma_up| more, which the bound grants to both.
+    tol = (5 e |D dt| + e |x1| + [noise] (e |noise sigma_up| + e |ref|)) (1 + 8e)
+  noise is ignored, as the kernel ignores it, unless sigma_up > 0.
+normal_bound, the N(0, 1) values of (seed, image, stream): element 4 g + j of an image is normal j of Philox group g.
+  The Philox4x32-10 words w come from the integer code of the CPU mirror (sampling/rng.py, pinned to the published
+  known-answer vectors in test_rng_cpu.py), the uniforms from the mirror's own fp32 _u01 and only then widened: the
+  fp32 rounding of (k + 0.5) 2^-24 for k >= 2^23 is part of the definition of the generator (u = 1.0 for k = 2^24 - 1),
+  a reference from the exact u is off by 2e-5 near u = 1. From there fp64 Box-Muller with the fp32 literal 6.2831853f:
+    r = sqrt(-2 ln u0), t = 2pi_f u1, z = r cos t, r sin t       (u0, u1 = words 0, 1 and 2, 3)
+  logf is off by LOGF_REL relative, the product by -2 is exact, sqrtf halves the relative error and rounds (e);
+  t = fl(2pi_f u1) <= 2 pi is off by e t <= 2 pi e, which moves cos and sin by as much; cosf and sinf add SINCOSF_REL
+  of a result <= 1; the product r cos t rounds once:
+    tol = e (A r + B |z|) (1 + 8e),  A = 2 pi + SINCOSF_REL / e,  B = 2 + LOGF_REL / (2 e)
+  u0 = 1.0 gives r = 0 and tol = 0: the value is an exact zero. bf16 output: _store_dt of that, u |ref| (1 + 2u) more.
+  Measured on the MI355X (test_sampling_bounds_gpu.py): max |y - ref| / tol = 0.40 over the 180 fp32 cases of
+  test_philox_randn_bound and 0.43 over the 17 x 2^20 values of test_philox_randn_block_cap (bf16: 0.99, the store
+  alone). The CPU mirror (glibc through torch) reaches 0.63 of e (7.3 r + |z|) over 4 images of 2^21 values.
+sampler_step_bound, cgs_sampler_step_dev: den = cfg_combine_bound (u given; else den = c, exact), then
+  euler_step_bound from the row's (sigma, sigma_down) with noise = normal_bound at stream = step scaled by
+  sup = fl(row[2] row[3]), rounded once as the kernel does; the errors of den and of the normals pass through their
+  slopes:  tol = (tol_euler + |dt / sigma| tol_den + sup tol_z) (1 + 8e). Returns (ref, tol) of x and of den_out.
+timestep_embedding_bound, cos / sin(a), a = t f, f = exp(-x), x = ln P k / half with ln P the fp32 value of logf(P):
+  -ln P k and the division by half round once each, __expf multiplies by the fp32 value of log2 e (its rounding and
+  that of the product): 4 e x in the exponent, relative after the exponential; v_exp_f32 adds EXP2_REL; t f rounds
+  once:  da = |t| f (EXP2_REL + 4 e (1 + x));  tol = da + SINCOSF_REL (|ref| + da);  t = 0: cos 0 = 1 and sin 0 = 0
+  are exact, tol = 0. Measured on the MI355X (test_timestep_embedding_bound, all 64 cases): max |y - ref| / tol = 0.35.
+silu_bound (cgs_silu, bf16 / fp16): x rcp(1 + __expf(-x)) is the SIG family's x rcp(1 + exp2(x a)) with the product
+  by log2 e inside __expf: act_err of the fused epilogues with d_pre = 0, one store in the dtype's u, and tiny(dtype)
+  for a result below the dtype's normal range.
+upsample_nearest2x moves bits: torch.equal against F.interpolate, no bound.
 """
 import math
 
@@ -205,6 +249,9 @@ RSQRT_REL = 4 * E        # rsqrtf (2 e) of var + eps formed by one division and 
 # the compiler, so these are supposed as well: 4 ulp for erff, 2 ulp for expf (1 ulp = 2 e).
 ERFF_REL = 8 * E         # erff (gelu_f)
 EXPF_REL = 4 * E         # expf (the SiLU of gn_f32_apply_kernel)
+# rng.hip and timestep_emb_kernel: supposed in the same way, 2 ulp each for logf and for sinf / cosf
+LOGF_REL = 4 * E         # logf (normal4)
+SINCOSF_REL = 4 * E      # sinf, cosf (normal4, timestep_emb_kernel), relative to a result <= 1
 TINY = {torch.bfloat16: 2.0 ** -126, torch.float16: 2.0 ** -25, torch.float32: 2.0 ** -126}
 
 
@@ -1296,3 +1343,155 @@ def f32_attn_inputs(B, heads, Sq, Sk, D, seed=0, device="cpu"):
         qkv[:, 32, 2 * HD:] = -SPIKE * s_h
     qkv = qkv.to(device)
     return qkv[:, :Sq, :HD], qkv[:, :Sk, HD:2 * HD], qkv[:, :Sk, 2 * HD:], s_h
+
+
+# ------------------------------------------------------------------------------------------------ sampling loop
+_M64, _M32 = (1 << 64) - 1, 0xFFFFFFFF
+TWO_PI_F = _f32(6.2831853)                       # the kernel's literal 6.2831853f
+NORMAL_A = 2 * math.pi + SINCOSF_REL / E         # tol = e (A r + B |z|), module docstring
+NORMAL_B = 2 + LOGF_REL / (2 * E)
+# flat sizes of the fp32 kernels: one element, both sides of a block of 256, several blocks with a ragged end; past
+# the 8192-block cap of ew_blocks (elementwise.hip) the grid-stride loop makes its second trip
+EW_SIZES = [1, 255, 256, 257, 4099]
+EW_CAP_N = 8192 * 256 + 513
+SILU_SIZES = [1, 7, 8, 9, 2055]                  # the scalar tail alone, no tail, one vector and a tail
+SILU_CAP_N = 8192 * 256 * 8 + 13                 # second trip and a tail in one call
+SEED63 = (1 << 63) + 5                           # a seed with bit 63 set
+# cgs_philox_randn: tails, image bases that are no multiple of 4 (the scalar store path), several images
+RNG_SHAPES = [(1, 1), (1, 3), (2, 5), (2, 1027), (3, 4, 8, 8)]
+RNG_SEEDS = [0, 1234567, SEED63, (1 << 64) - 1]
+RNG_INDEX0 = [0, (1 << 31) - 1, 1 << 40]
+RNG_STREAMS = [0, (1 << 32) + 7, (1 << 63) - 1]
+RNG_CAP_SHAPE = (17, 1 << 20)                    # 17 * 2^18 groups: past the 16384-block cap of rng_blocks (rng.hip)
+TEMB_SHAPES = [(1, 2), (5, 6), (3, 320), (2, 1280)]
+TEMB_T = [0.0, 0.5, 999.0, 1000.0]
+
+
+def _sc(v):
+    """A scalar as the fp32 value the kernel is passed (an fp32 tensor element is taken as it is)."""
+    return float(v) if torch.is_tensor(v) else _f32(v)
+
+
+def cfg_combine_bound(c, u, s):
+    """out = u + (c - u) s in fp32 (cgs_cfg_combine, the den of cgs_sampler_step_dev)."""
+    c, u, s = f64(c), f64(u), _sc(s)
+    ref = u + (c - u) * s
+    return ref, (2 * E * (c - u).abs() * abs(s) + E * ref.abs()) * (1 + 2 * E)
+
+
+def euler_step_bound(x, den, noise, sigma, sigma_down, sigma_up):
+    """x + (x - den) / sigma (sigma_down - sigma) + noise sigma_up in fp32 (cgs_euler_step and the fused forms);
+    noise None, or sigma_up <= 0: no noise term."""
+    x, den = f64(x), f64(den)
+    s, sd, sup = _sc(sigma), _sc(sigma_down), _sc(sigma_up)
+    ddt = (x - den) / s * (sd - s)
+    ref = x + ddt
+    tol = 5 * E * ddt.abs() + E * ref.abs()
+    if noise is not None and sup > 0:
+        q = f64(noise) * sup
+        ref = ref + q
+        tol = tol + E * q.abs() + E * ref.abs()
+    return ref, tol * (1 + 8 * E)
+
+
+def philox_words(seed, inds, groups, stream):
+    """The four Philox4x32-10 output words [len(inds), groups] (int64) of every element group, from the integer code
+    of the CPU mirror: key = image_key(seed, index), counter = (group lo, hi, stream lo, hi)."""
+    from comfy_gen_server_amd.sampling import rng
+    inds = [int(i) for i in inds]
+    k0, k1 = rng._key_tensors(seed, inds)
+    g = torch.arange(groups, dtype=torch.int64).view(1, -1)
+    s = int(stream) & _M64
+    c0 = (g & _M32).expand(len(inds), -1)
+    c1 = (g >> 32).expand(len(inds), -1)
+    c2, c3 = torch.full_like(c0, s & _M32), torch.full_like(c0, s >> 32)
+    return rng._philox10(c0, c1, c2, c3, k0.expand_as(c0), k1.expand_as(c0))
+
+
+def normal_bound(seed, inds, n, stream, dtype=torch.float32):
+    """(ref, tol) [len(inds), n] of the N(0, 1) values of (seed, image, stream): fp64 Box-Muller on the mirror's
+    fp32 uniforms (module docstring). dtype bfloat16: the store of cgs_philox_randn's bf16 form."""
+    from comfy_gen_server_amd.sampling import rng
+    groups = (n + 3) // 4
+    un = [rng._u01(w).double() for w in philox_words(seed, inds, groups, stream)]
+    refs, tols = [], []
+    for u0, u1 in ((un[0], un[1]), (un[2], un[3])):
+        r = torch.sqrt(-2.0 * torch.log(u0))
+        t = TWO_PI_F * u1
+        for trig in (torch.cos, torch.sin):
+            z = r * trig(t)
+            refs.append(z)
+            tols.append(E * (NORMAL_A * r + NORMAL_B * z.abs()) * (1 + 8 * E))
+    ref = torch.stack(refs, -1).reshape(len(un[0]), groups * 4)[:, :n].contiguous()
+    tol = torch.stack(tols, -1).reshape(len(un[0]), groups * 4)[:, :n].contiguous()
+    if dtype != torch.float32:
+        tol = _store_dt(ref, tol, dtype)
+    return ref, tol
+
+
+def sampler_step_bound(x, c, u, cfg, row, seed, index0, step):
+    """cgs_sampler_step_dev on fp32 x, c, u (None: den = c) [B, ...] with row = params[step] = (sigma, sigma_down,
+    sigma_up, s_noise, ...) in fp32. Returns ((ref, tol) of x, (ref, tol) of den_out)."""
+    row = row.detach().to("cpu", torch.float32)
+    s, sd, sup = float(row[0]), float(row[1]), float(row[2] * row[3])        # the fp32 product, rounded once
+    if u is None:
+        den = f64(c)
+        dtol = torch.zeros_like(den)
+    else:
+        den, dtol = cfg_combine_bound(c, u, cfg)
+    z, extra = None, abs((sd - s) / s) * dtol
+    if sup > 0:
+        B = x.shape[0]
+        z, ztol = normal_bound(seed, range(int(index0), int(index0) + B), x[0].numel(), step)
+        z, ztol = z.reshape(x.shape).to(x.device), ztol.reshape(x.shape).to(x.device)
+        extra = extra + sup * ztol
+    ref, tol = euler_step_bound(x, den, z, s, sd, sup)
+    return (ref, (tol + extra) * (1 + 8 * E)), (den, dtol)
+
+
+def timestep_embedding_bound(t, dim, max_period=10000.0, flip=True):
+    """[cos | sin] (flip) or [sin | cos] of t exp(-ln P k / half), k < half = dim // 2, for fp32 t [n]."""
+    t = f64(t.detach().float())
+    half = dim // 2
+    lnp = float(torch.log(torch.tensor(float(max_period), dtype=torch.float32)))
+    xk = lnp * torch.arange(half, dtype=torch.float64, device=t.device) / half
+    a = t[:, None] * torch.exp(-xk)[None]
+    da = a.abs() * (EXP2_REL + 4 * E * (1 + xk))[None]
+    c, s = torch.cos(a), torch.sin(a)
+    tc, ts = (da + SINCOSF_REL * (v.abs() + da) for v in (c, s))
+    exact = (t == 0)[:, None]
+    tc, ts = tc.masked_fill(exact, 0.0), ts.masked_fill(exact, 0.0)
+    if flip:
+        return torch.cat([c, s], -1), torch.cat([tc, ts], -1)
+    return torch.cat([s, c], -1), torch.cat([ts, tc], -1)
+
+
+def silu_bound(x):
+    """cgs_silu on bf16 / fp16 x: the SIG-family activation error and one store in x's dtype."""
+    ref, tol = _act_tol(f64(x), 0.0, None, "silu", 0.0, dtype=x.dtype)
+    return ref, tol + TINY[x.dtype]
+
+
+def ew_inputs(n, seed=0, device="cpu"):
+    """Four fp32 vectors of n elements (x, cond / den, uncond, noise) = randn s with the scales log-spaced over
+    1e-3 .. 10 and permuted; the last x is a spike of 48, and in the middle den == x (a difference of exactly 0)."""
+    g = torch.Generator().manual_seed(seed)
+    x, c, u, z = (torch.randn(n, generator=g) * mixed_scales(n, g) for _ in range(4))
+    x[n - 1] = SPIKE
+    c[n // 2] = x[n // 2]
+    return tuple(v.to(device) for v in (x, c, u, z))
+
+
+def silu_inputs(n, dtype, seed=0, device="cpu"):
+    """4 randn in ``dtype``; the first elements are +-0, +-48 and the largest and smallest normal of the dtype, both
+    signs; the last two (the scalar tail where n % 8 >= 2) -48 and the smallest normal."""
+    g = torch.Generator().manual_seed(seed)
+    fi = torch.finfo(dtype)
+    x = torch.randn(n, generator=g) * 4
+    special = torch.tensor([0.0, -0.0, SPIKE, -SPIKE, fi.max, -fi.max, fi.tiny, -fi.tiny], dtype=torch.float64)
+    k = min(n, special.numel())
+    x = x.double()
+    x[:k] = special[:k]
+    if n > special.numel() + 2:
+        x[n - 1], x[n - 2] = -SPIKE, fi.tiny
+    return x.to(dtype).to(device)

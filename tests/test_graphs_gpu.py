@@ -77,10 +77,12 @@ def test_graphs_cpu_is_eager():
 def test_step_graph_matches_eager_loop(cuda, monkeypatch, sampler):
     """One captured graph per sampler step (UNet(cond||uncond) + CFG + Euler(-a) + in-register noise,
     every scalar from a device table) reproduces the eager Python loop, for two jobs through the
-    same plan (second job = pure replay with a new seed, prompt latents and global image offset)."""
+    same plan (second job = pure replay with a new seed, prompt latents and global image offset).
+    euler_ancestral runs a third job whose seed has bit 63 set: the device table keeps all 64 bits."""
     from comfy_gen_server_amd.tools.synth import build_pipeline
     from comfy_gen_server_amd.parallel.dp import Job, generate_local
     from comfy_gen_server_amd.sampling import step_graph
+    jobs = ((5, 0), (9, 3)) + ((((1 << 63) + 5, 1),) if sampler == "euler_ancestral" else ())
     with torch.inference_mode():
         patcher, clip, vae = build_pipeline("tiny", device=cuda, dtype=torch.bfloat16, seed=2)
         res = {}
@@ -88,13 +90,14 @@ def test_step_graph_matches_eager_loop(cuda, monkeypatch, sampler):
         for mode in ("0", "1"):
             monkeypatch.setenv("CGS_GRAPHS", mode)
             outs = []
-            for seed, off in ((5, 0), (9, 3)):
+            for seed, off in jobs:
                 job = Job(batch=3, steps=6, cfg=6.0, sampler=sampler, width=64, height=64, seed=seed)
                 outs.append(generate_local(patcher, clip, vae, job, off, 3, decode=False).float())
             res[mode] = outs
         torch.cuda.synchronize()
     assert step_graph.stats["capture"] - before["capture"] >= 1
-    assert step_graph.stats["replay"] - before["replay"] >= 12 and step_graph.stats["jobs"] - before["jobs"] == 2
+    assert step_graph.stats["replay"] - before["replay"] >= 12
+    assert step_graph.stats["jobs"] - before["jobs"] == len(jobs)
     for a, b in zip(res["0"], res["1"]):
         err = (a - b).abs().max().item()
         assert err < 2e-2 * (a.abs().max().item() + 1), err
@@ -390,22 +393,24 @@ RUN_GRAPH_SAMPLERS = ["heun", "dpm_2", "dpm_2_ancestral", "lms", "dpmpp_2s_ances
 def test_run_graph_replay_matches_eager(cuda, monkeypatch, sampler):
     """Samplers outside the fused Euler-family step graph replay whole runs from one hipGraph per step
     (run_graph.py): the first run of a plan is eager, the second captures, later ones replay. Replays for
-    two seeds (device-resident noise key) equal the eager loop of the same seeds."""
+    two seeds (device-resident noise key) equal the eager loop of the same seeds. dpm_2_ancestral replays a
+    further job whose seed has bit 63 set: the key tensor keeps all 64 bits."""
     from comfy_gen_server_amd.sampling import run_graph, samplers
     from comfy_gen_server_amd.tools.synth import build_pipeline
     if sampler not in samplers.KSampler.SAMPLERS:
         pytest.skip(f"{sampler} not in this sampler list")
+    more = [(1 << 63) + 5] if sampler == "dpm_2_ancestral" else []
     monkeypatch.setenv("CGS_GRAPHS", "1")
     with torch.inference_mode():
         patcher, clip, vae = build_pipeline("tiny", device=cuda, dtype=torch.bfloat16, seed=2)
         monkeypatch.setenv("CGS_RUN_GRAPHS", "0")
-        ref5, ref6 = _run_jobs(patcher, clip, vae, sampler, [5, 6])
+        ref5, ref6, *ref_more = _run_jobs(patcher, clip, vae, sampler, [5, 6] + more)
         monkeypatch.setenv("CGS_RUN_GRAPHS", "1")
         before = dict(run_graph.stats)
-        _, g6, g5 = _run_jobs(patcher, clip, vae, sampler, [5, 6, 5])
+        _, g6, g5, *g_more = _run_jobs(patcher, clip, vae, sampler, [5, 6, 5] + more)
     assert run_graph.stats["capture"] - before["capture"] == 1, run_graph.stats
-    assert run_graph.stats["replay_runs"] - before["replay_runs"] == 2, run_graph.stats
-    for got, want in ((g6, ref6), (g5, ref5)):
+    assert run_graph.stats["replay_runs"] - before["replay_runs"] == 2 + len(more), run_graph.stats
+    for got, want in [(g6, ref6), (g5, ref5)] + list(zip(g_more, ref_more)):
         err = ((got - want).norm() / want.norm()).item()
         assert err < 1e-2, err
     assert ((g5 - g6).norm() / g5.norm()).item() > 1e-2      # the seed reached the replayed noise

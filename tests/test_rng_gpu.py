@@ -1,7 +1,7 @@
 """Device RNG kernels (csrc/kernels/rng.hip, K18) vs their bit-exact torch mirror (sampling/rng.py).
 
-The uniforms are 24-bit exact on both sides; only libm-level differences of log/sin/cos remain,
-so the tolerance is a few fp32 ulps."""
+The 24-bit uniforms are identical on both sides; only libm-level differences of log/sin/cos remain,
+so the tolerance is a few fp32 ulps. test_sampling_bounds_gpu.py holds the same kernels to derived bounds."""
 import pytest
 import torch
 
