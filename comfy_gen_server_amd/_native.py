@@ -173,6 +173,11 @@ KERNEL_SIGNATURES = {
     # ... + CgsAct code, parameter: act(conv + bias) (+ res) on the mc::tile kernels (variant 3 / 4 / 8)
     "cgs_conv2d_nhwc_act": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F,
                             _P],
+    # 3 x 3 conv on channel slices of wider NHWC buffers (csrc/kernels/dense.hip): x, pitch, image stride; w, bias;
+    # res, pitch, stride; res2, pitch, stride; out, pitch, stride; N, H, W, Cin, Cout; CgsAct code, parameter;
+    # alpha, beta; stream. out = alpha act(conv + bias) + beta res + res2
+    "cgs_conv3x3_slice": [_P, _I, _L, _P, _P, _P, _I, _L, _P, _I, _L, _P, _I, _L, _I, _I, _I, _I, _I, _I, _F, _F, _F,
+                          _P],
     # counter-based noise keyed by (seed, global image index, stream) (csrc/kernels/rng.hip, K18)
     "cgs_philox_randn": [_P, _I, _L, ctypes.c_ulonglong, _L, ctypes.c_ulonglong, _P, _F, _I, _P, _P],
     "cgs_euler_ancestral_philox": [_P, _P, _I, _L, _F, _F, _F, ctypes.c_ulonglong, _L, ctypes.c_ulonglong, _P, _P],

@@ -13,13 +13,19 @@ that loads there loads here.
 from __future__ import annotations
 
 import math
+import os
 import re
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .layers import Conv2d
+from .. import ops
+from .layers import Conv2d, _hooked
+
+# Whether the dense blocks take the slice-conv path when CGS_DENSE_CONV is unset. On: one RRDB (64, 32) at 512^2 ran
+# in 1113 us against 2037 us, 174 times the old path's own spread (profiles/r13/dense_block.md).
+_DENSE_DEFAULT = True
 
 
 class UnsupportedModel(Exception):
@@ -40,10 +46,69 @@ class ResidualDenseBlock5C(nn.Module):
             setattr(self, f"conv{i + 1}", nn.Sequential(Conv2d(cin, cout, 3, padding=1)))
 
     def forward(self, x):
+        if self.dense_ok(x):
+            buf = self.dense_buffer(x)
+            buf[:, :self.nf].copy_(x)
+            return self.forward_dense(buf, _plain_like(x))
         feats = [x]
         for i in range(4):
             feats.append(_conv_lrelu(getattr(self, f"conv{i + 1}")[0], torch.cat(feats, 1) if len(feats) > 1 else x))
         return self.conv5[0](torch.cat(feats, 1)) * 0.2 + x
+
+    # The dense path (``ops.conv2d_into``): the block's feature stack lives in one channels-last [N, nf + 4 gc, H, W]
+    # buffer. Conv i reads the channel prefix [0, nf + (i - 1) gc) and writes its gc outputs behind it; nothing is
+    # concatenated, and the scale-and-add is conv5's epilogue.
+    @property
+    def nf(self):
+        return self.conv1[0].in_channels
+
+    @property
+    def gc(self):
+        return self.conv1[0].out_channels
+
+    def dense_ok(self, x) -> bool:
+        """Device, bf16, unhooked weights of the activation dtype, nf % 32 == 0, gc % 16 == 0, gc <= 64 -- and
+        ``CGS_DENSE_CONV`` (read per call: ``1`` the dense path wherever it is legal, ``0`` never, unset
+        ``_DENSE_DEFAULT``)."""
+        mode = os.environ.get("CGS_DENSE_CONV", "")
+        if mode == "0" or (mode != "1" and not _DENSE_DEFAULT):
+            return False
+        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and self.nf % 32 == 0 and self.gc % 16 == 0
+                and self.gc <= 64 and x.shape[1] == self.nf):
+            return False
+        convs = [getattr(self, f"conv{i + 1}")[0] for i in range(5)]
+        if any(_hooked(c) or c.weight.dtype != x.dtype or c.weight.device != x.device
+               or (c.bias is not None and c.bias.dtype != x.dtype) for c in convs):
+            return False
+        return ops.core._spatial() is None and ops.backend_for("conv", x, "cgs_conv3x3_slice") == "hip"
+
+    def dense_buffer(self, x):
+        """An empty feature buffer for this block at x's batch and size; its channels [0, nf) take the input."""
+        return torch.empty((x.shape[0], self.nf + 4 * self.gc, x.shape[2], x.shape[3]), device=x.device,
+                           dtype=x.dtype, memory_format=torch.channels_last)
+
+    def forward_dense(self, buf, out, outer=None):
+        """``buf``: this block's feature buffer with the input x in channels [0, nf). Writes ``0.2 conv5 + x`` into
+        the view ``out`` (the next block's input slot, or a plain tensor) and returns it; with ``outer`` (the
+        RRDB's input x0, for its third block) ``0.2 (0.2 conv5 + x) + x0``. ``out`` and ``outer`` lie outside buf."""
+        nf, gc = self.nf, self.gc
+        for i in range(4):
+            c = getattr(self, f"conv{i + 1}")[0]
+            ops.conv2d_into(buf[:, :nf + i * gc], c.weight, c.bias, buf[:, nf + i * gc:nf + (i + 1) * gc],
+                            weight_nhwc=c.weight_nhwc(), act="leaky_relu", act_param=0.2)
+        c, x = self.conv5[0], buf[:, :nf]
+        if nf > 64:      # wider than the slice kernel's outputs (SPSR): the ordinary conv over the whole buffer
+            y = c(buf) * 0.2 + x
+            out.copy_(y if outer is None else y * 0.2 + outer)
+            return out
+        if outer is None:
+            return ops.conv2d_into(buf, c.weight, c.bias, out, weight_nhwc=c.weight_nhwc(), alpha=0.2, residual=x)
+        return ops.conv2d_into(buf, c.weight, c.bias, out, weight_nhwc=c.weight_nhwc(), alpha=0.2 * 0.2, residual=x,
+                               beta=0.2, residual2=outer)
+
+
+def _plain_like(x):
+    return torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
 
 
 class RRDB(nn.Module):
@@ -54,7 +119,25 @@ class RRDB(nn.Module):
         self.RDB3 = ResidualDenseBlock5C(nf, gc)
 
     def forward(self, x):
+        if self.dense_ok(x):
+            buf = self.RDB1.dense_buffer(x)
+            buf[:, :self.RDB1.nf].copy_(x)
+            return self.forward_dense(buf, _plain_like(x))
         return self.RDB3(self.RDB2(self.RDB1(x))) * 0.2 + x
+
+    def dense_ok(self, x) -> bool:
+        return all(b.dense_ok(x) for b in (self.RDB1, self.RDB2, self.RDB3))
+
+    def forward_dense(self, buf, out):
+        """``buf``: RDB1's feature buffer with x0 in channels [0, nf); ``out``: where ``0.2 RDB3(..) + x0`` goes (the
+        next RRDB's input slot or a plain tensor). Each block's conv5 writes into the next block's buffer, so four
+        buffers are live at most: buf (x0 is RDB3's second residual), two of its own, and out's."""
+        nf = self.RDB1.nf
+        b2 = self.RDB2.dense_buffer(buf)
+        self.RDB1.forward_dense(buf, b2[:, :nf])
+        b3 = self.RDB3.dense_buffer(buf)
+        self.RDB2.forward_dense(b2, b3[:, :nf])
+        return self.RDB3.forward_dense(b3, out, outer=buf[:, :nf])
 
 
 class _Trunk(nn.Module):
@@ -65,6 +148,17 @@ class _Trunk(nn.Module):
         self.sub = nn.ModuleList([RRDB(nf, gc) for _ in range(nb)] + [Conv2d(nf, nf, 3, padding=1)])
 
     def forward(self, x):
+        blocks = list(self.sub[:-1])
+        if blocks and all(m.dense_ok(x) for m in blocks):
+            # every RRDB writes its result straight into the next one's feature buffer, the last into a plain tensor
+            nf = x.shape[1]
+            buf = blocks[0].RDB1.dense_buffer(x)
+            buf[:, :nf].copy_(x)
+            for i, m in enumerate(blocks):
+                nxt = _plain_like(x) if i + 1 == len(blocks) else blocks[i + 1].RDB1.dense_buffer(x)
+                m.forward_dense(buf, nxt[:, :nf])
+                buf = nxt
+            return self.sub[-1](buf, residual=x)
         h = x
         for m in self.sub[:-1]:
             h = m(h)

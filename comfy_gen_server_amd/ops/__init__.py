@@ -16,7 +16,7 @@ from .dispatch import (  # noqa: F401
 )
 from .core import (  # noqa: F401
     linear, linear_geglu, attention, attention_lse, attention_kv2, attention_bias, group_norm, layer_norm, conv2d,
-    conv_transpose2d, conv_transpose_phase_weights, silu, gelu, activation, ACT_CODES,
+    conv2d_into, conv_slice_layout, conv_transpose2d, conv_transpose_phase_weights, silu, gelu, activation, ACT_CODES,
     upsample_nearest2x, timestep_embedding, cfg_combine, euler_step, depthwise_conv2d_nhwc,
     depthwise_conv2d_nhwc_lnstats,
     interpolate, fused_bias_act, channel_affine_nhwc, channel_affine_layernorm_nhwc, upfirdn2d, upfirdn2d_reference, vq_nearest, grn_nhwc,

@@ -1238,6 +1238,135 @@ def _conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, st
     return y
 
 
+def conv_slice_layout(shape, strides, storage_offset):
+    """How cgs_conv3x3_slice is given a [N, C, H, W] view of ``shape`` / ``strides`` / ``storage_offset`` (elements):
+    ``(pixel pitch, image stride, ok)``. Pure: no tensor is touched.
+
+    ``ok`` means a channel slice of an NHWC buffer the kernel can address: unit channel stride, pixel pitch P =
+    stride(3) >= C, rows and images packed (stride(2) = W P, stride(0) = H W P; the stride of a size-1 dimension is
+    free), and 16-byte vectors possible -- P and the storage offset multiples of 8 elements. ``buf[:, :96]`` and
+    ``buf[:, 96:128]`` of a channels-last ``[N, 192, H, W]`` buffer qualify, and so does the buffer itself (P = C)."""
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) != 4 or len(strides) != 4 or min(shape) < 1:
+        return 0, 0, False
+    N, C, H, W = shape
+    sn, sc, sh, sw = strides
+    P = sw if W > 1 else (sh // W if H > 1 else (sn // (H * W) if N > 1 else (C + 7) // 8 * 8))
+    ok = (C == 1 or sc == 1) and P >= C and (W == 1 or sw == P) and (H == 1 or sh == W * P) \
+        and (N == 1 or sn == H * W * P) and P % 8 == 0 and int(storage_offset) % 8 == 0
+    return P, H * W * P, ok
+
+
+def _slice_channels(t):
+    """``(pitch, first channel)`` of a view on the pixel lattice of its buffer, or None where it is not one."""
+    P, _, _ = conv_slice_layout(t.shape, t.stride(), 0)
+    N, C, H, W = t.shape
+    lattice = (C == 1 or t.stride(1) == 1) and P >= C and (W == 1 or t.stride(3) == P) \
+        and (H == 1 or t.stride(2) == W * P) and (N == 1 or t.stride(0) == H * W * P)
+    c0 = t.storage_offset() % P if lattice and P > 0 else 0
+    return (P, c0) if lattice and c0 + C <= P else None
+
+
+def _same_view(a, b) -> bool:
+    return (a.data_ptr() == b.data_ptr() and a.dtype == b.dtype and tuple(a.shape) == tuple(b.shape)
+            and all(sa == sb for sa, sb, n in zip(a.stride(), b.stride(), a.shape) if n > 1))
+
+
+def _views_overlap(a, b) -> bool:
+    """Whether two [N, C, H, W] views share an element. Exact for channel slices of one NHWC buffer (same pitch, the
+    same pixels: then only the channel ranges decide); every other pair that shares storage and whose address
+    ranges meet counts as overlapping."""
+    if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return False
+    span = lambda t: 1 + sum((n - 1) * s for n, s in zip(t.shape, t.stride()))      # noqa: E731
+    a0, b0 = a.storage_offset() * a.element_size(), b.storage_offset() * b.element_size()
+    if a0 + span(a) * a.element_size() <= b0 or b0 + span(b) * b.element_size() <= a0:
+        return False
+    la, lb = _slice_channels(a), _slice_channels(b)
+    if (la is None or lb is None or la[0] != lb[0] or a.dtype != b.dtype or tuple(a.shape[2:]) != tuple(b.shape[2:])
+            or a.shape[0] != b.shape[0]):
+        return True
+    return la[1] < lb[1] + b.shape[1] and lb[1] < la[1] + a.shape[1]
+
+
+def conv2d_into(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, out: torch.Tensor, *,
+                weight_nhwc: torch.Tensor | None = None, act: str | None = None, act_param: float = 0.0,
+                alpha: float = 1.0, residual: torch.Tensor | None = None, beta: float = 1.0,
+                residual2: torch.Tensor | None = None) -> torch.Tensor:
+    """3 x 3 / stride 1 / pad 1 conv between channel slices of NHWC buffers, written in place:
+
+        out[...] = alpha * act(conv2d(x, weight) + bias) + beta * residual + residual2
+
+    ``x``, ``out``, ``residual``, ``residual2`` are [N, C, H, W] views, typically ``buf[:, :96]`` / ``buf[:, 96:128]``
+    of one channels-last buffer (``conv_slice_layout``), so a dense block grows its feature stack without a
+    ``torch.cat``. Returns ``out``. Aliasing (ValueError, nothing is launched): ``out`` shares no element with ``x``
+    -- in one buffer its channel range lies apart from the channels read; ``residual`` / ``residual2`` are the
+    identical view as ``out`` or share no element with it.
+
+    Device, bf16, Cin % 32 == 0, Cout in {16, 32, 48, 64}, every view a slice the kernel can address and
+    ``weight_nhwc`` ([Cout, 3, 3, Cin]) given: cgs_conv3x3_slice (csrc/kernels/dense.hip), epilogue in fp32 with one
+    rounding at the store. No host synchronisation and no allocation: capturable. Everything else takes the torch
+    path, the oracle: the conv and the formula in fp32, then ``out.copy_``."""
+    if act is not None and act not in ACT_CODES:
+        raise ValueError(f"unknown activation {act!r} (one of {sorted(ACT_CODES)})")
+    if x.dim() != 4 or out.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"conv2d_into takes 4-D views and a 3 x 3 weight, got x {tuple(x.shape)}, out "
+                         f"{tuple(out.shape)}, weight {tuple(weight.shape)}")
+    N, Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    if weight.shape[1] != Cin or tuple(out.shape) != (N, Cout, H, W):
+        raise ValueError(f"conv2d_into: x {tuple(x.shape)} and weight {tuple(weight.shape)} do not give out "
+                         f"{tuple(out.shape)}")
+    if bias is not None and tuple(bias.shape) != (Cout,):
+        raise ValueError(f"conv2d_into: bias {tuple(bias.shape)} for {Cout} output channels")
+    for name, r in (("residual", residual), ("residual2", residual2)):
+        if r is None:
+            continue
+        if tuple(r.shape) != tuple(out.shape):
+            raise ValueError(f"conv2d_into: {name} {tuple(r.shape)} does not match out {tuple(out.shape)}")
+        if not _same_view(r, out) and _views_overlap(r, out):
+            raise ValueError(f"conv2d_into: {name} overlaps out without being the same view")
+    if _views_overlap(x, out):
+        raise ValueError("conv2d_into: out overlaps the channels that the conv reads")
+    be = backend_for("conv", x, "cgs_conv3x3_slice")
+    views = (x, out) + tuple(r for r in (residual, residual2) if r is not None)
+    if (be == "hip" and weight_nhwc is not None and Cin % 32 == 0 and Cout % 16 == 0 and 16 <= Cout <= 64
+            and all(t.dtype == torch.bfloat16 and t.device == x.device for t in views + (weight_nhwc,))
+            and (bias is None or (bias.dtype == torch.bfloat16 and bias.is_contiguous()))
+            and weight_nhwc.is_contiguous() and tuple(weight_nhwc.shape) == (Cout, 3, 3, Cin)
+            and weight_nhwc.data_ptr() % 16 == 0):
+        lay = [conv_slice_layout(t.shape, t.stride(), t.storage_offset()) for t in views]
+        if all(ok and t.data_ptr() % 16 == 0 for (_, _, ok), t in zip(lay, views)):
+            count("conv", "hip")
+            count("conv_dense", "hip")
+            if act is not None:
+                count("act_fused", "hip")
+            it = iter(zip(views[2:], lay[2:]))
+            (r1, l1) = next(it) if residual is not None else (None, (0, 0, True))
+            (r2, l2) = next(it) if residual2 is not None else (None, (0, 0, True))
+            _check(_lib().cgs_conv3x3_slice(x.data_ptr(), lay[0][0], lay[0][1], weight_nhwc.data_ptr(), _ptr(bias),
+                                            _ptr(r1), l1[0], l1[1], _ptr(r2), l2[0], l2[1], out.data_ptr(), lay[1][0],
+                                            lay[1][1], N, H, W, Cin, Cout, ACT_CODES[act] if act else 0,
+                                            float(act_param), float(alpha), float(beta), _stream()),
+                   "cgs_conv3x3_slice")
+            return out
+    if be == "torch":
+        count("conv", "torch")
+    else:
+        vendor_fallback("conv", f"conv2d_into dtype {x.dtype}, Cin={Cin}, Cout={Cout}, pitches "
+                                f"{[t.stride(3) for t in views]}")
+    y = F.conv2d(x.float(), weight.float(), None if bias is None else bias.float(), 1, 1)
+    if act is not None:
+        y = _act_torch(y, act, float(act_param))
+    y = alpha * y
+    if residual is not None:
+        y = y + beta * residual.float()
+    if residual2 is not None:
+        y = y + residual2.float()
+    out.copy_(y)
+    return out
+
+
 # ConvTranspose2d(k=4, s=2, p=1) as four sub-pixel phases: output pixel (2y + py, 2x + px) sums the
 # 2 x 2 input neighbourhood starting at (y - 1 + py, x - 1 + px) through kernel taps _CT_TAPS[py] x
 # _CT_TAPS[px] (tap k of the transposed conv reaches output 2i - 1 + k).
