@@ -45,7 +45,12 @@ def _stale(src, obj, deps=()):
 # Private-memory (scratch) budget of the MFMA main-loop kernels, bytes per lane. A kernel whose
 # accumulator / fragment arrays fall out of registers (SROA failing on a grown epilogue) runs ~10x
 # slower with identical results -- round 3 shipped one such v7 build -- so the build fails instead.
-SCRATCH_BUDGET = {"gemm_bf16_nt_v7_kernel": 128, "conv_nhwc_v7_kernel": 128, "attn_fwd_d64": 64}
+SCRATCH_BUDGET = {"gemm_bf16_nt_v7_kernel": 128, "conv_nhwc_v7_kernel": 128, "attn_fwd_d64": 64,
+                  "window_attn_kernel": 0}
+
+# Extra compiler flags of single sources. window_attn.hip: no packed fp32 VALU ops (v_pk_add / mul / fma_f32) in its
+# score and softmax arithmetic.
+EXTRA_FLAGS = {"window_attn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _resources(out):
@@ -97,7 +102,7 @@ def build_kernels(verbose=False):
         o = os.path.join(BUILD, os.path.basename(s) + ".o")
         objs.append(o)
         if _stale(s, o, headers):
-            jobs.append([HIPCC] + flags + ["-c", s, "-o", o])
+            jobs.append([HIPCC] + flags + EXTRA_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o])
     report = {}
     with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         for out in ex.map(_run, jobs):

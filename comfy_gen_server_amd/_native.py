@@ -92,6 +92,9 @@ KERNEL_SIGNATURES = {
     # 2 bf16), mask strides (b, h, q; elements, 0 broadcasts), key_mask, causal, stream
     "cgs_flash_attn_fwd_mask": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
                                 _F, _P, _I, _L, _L, _L, _P, _I, _P],
+    # fused shifted-window attention (window_attn.hip): qkv [B, H*W, 3C], o [B, H*W, C], table [(2ws-1)^2, heads],
+    # scale, cosine, hscale [heads] or null, B, H, W, heads, D, ws, shift, stream
+    "cgs_window_attn_fwd": [_P, _P, _P, _F, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     # same + fp32 LSE [B, H, Sq] out (ring attention merge): q,k,v,o,lse, B,H,Sq,Sk,D, 12 strides, scale
     "cgs_flash_attn_fwd_lse": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
                                _F, _P],

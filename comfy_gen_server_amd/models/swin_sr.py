@@ -4,8 +4,10 @@
 position bias / SwinV2 scaled-cosine attention with the continuous position-bias MLP, the
 residual Swin transformer blocks, and every upsampler head the reference detects).
 
-Layout: activations stay token-major ``[B, H*W, C]`` between blocks; a block rolls and
-partitions the ``[B, H, W, C]`` view into ``ws x ws`` windows, runs one batched attention over
+Layout: activations stay token-major ``[B, H*W, C]`` between blocks. SwinIR / Swin2SR / HAT blocks with 8 x 8 or
+16 x 16 windows project qkv where the tokens lie and call ``ops.window_attention`` (``CGS_WINDOW_ATTN``), whose
+kernel does the cyclic shift, the windows, the position bias and the shift mask in its addressing; elsewhere a
+block rolls and partitions the ``[B, H, W, C]`` view into ``ws x ws`` windows, runs one batched attention over
 ``B * nW`` windows (fp32 softmax), and reverses. Linear layers are ``layers.Linear`` (HIP GEMM
 on the device), convs are ``layers.Conv2d`` (NHWC implicit-GEMM MFMA kernel). The relative
 position index, the shifted-window mask and the SwinV2 coordinate table are derived from the
@@ -111,13 +113,36 @@ class WindowAttention(nn.Module):
         N = self.ws * self.ws
         return bias.view(N, N, self.heads).permute(2, 0, 1)
 
+    def _qkv(self, x: torch.Tensor) -> torch.Tensor:
+        if self.v2 and self.q_bias is not None:
+            return self.qkv(x) + torch.cat([self.q_bias, torch.zeros_like(self.v_bias), self.v_bias]).to(x.dtype)
+        return self.qkv(x)
+
+    def fused_ok(self, x: torch.Tensor, hw, shift: int) -> bool:
+        """The image-level entry serves these tokens: the switch is on for this window size and the shapes are
+        in ``ops.window_attention``'s domain (on the device: bf16, the fused kernel)."""
+        if not (ops.window_attention_enabled(self.ws)
+                and ops.window_attention_domain(hw, self.ws, shift, self.heads, self.dim // self.heads)):
+            return False
+        return x.device.type == "cpu" or (x.dtype == torch.bfloat16
+                                          and ops.backend_for("window_attention", x, "cgs_window_attn_fwd") == "hip")
+
+    def forward_image(self, x: torch.Tensor, hw, shift: int) -> torch.Tensor:
+        """Tokens [B, H*W, C] of the whole image, un-rolled and un-partitioned: the qkv projection is per token, so
+        it runs where the tokens lie and ``ops.window_attention`` does the shift, the windows and the score terms."""
+        if self.v2:
+            table = 16 * torch.sigmoid(self.cpb_mlp(self.coords_table.to(self.cpb_mlp[0].weight.dtype)).float())
+            o = ops.window_attention(self._qkv(x), hw, self.ws, shift, self.heads, table, scale=1.0, cosine=True,
+                                     head_scale=torch.clamp(self.logit_scale.float(), max=math.log(100.0)).exp())
+        else:
+            o = ops.window_attention(self._qkv(x), hw, self.ws, shift, self.heads,
+                                     self.relative_position_bias_table.float(), scale=self.scale)
+        return self.proj(o)
+
     def forward(self, x: torch.Tensor, mask: torch.Tensor | None) -> torch.Tensor:
         Bw, N, C = x.shape
         h = self.heads
-        if self.v2 and self.q_bias is not None:
-            qkv = self.qkv(x) + torch.cat([self.q_bias, torch.zeros_like(self.v_bias), self.v_bias]).to(x.dtype)
-        else:
-            qkv = self.qkv(x)
+        qkv = self._qkv(x)
         q, k, v = qkv.view(Bw, N, 3, h, C // h).permute(2, 0, 3, 1, 4).unbind(0)
         if self.v2:     # cosine scores: unit q / k, the per-head logit scale on the fp32 scores
             q = F.normalize(q.float(), dim=-1).to(v.dtype)
@@ -156,6 +181,8 @@ class SwinBlock(nn.Module):
         H, W = hw
         B, L, C = x.shape
         ws, sh = self.ws, self.shift
+        if self.attn.fused_ok(x, hw, sh):
+            return self.attn.forward_image(x, hw, sh)
         y = x.view(B, H, W, C)
         if sh:
             y = torch.roll(y, (-sh, -sh), (1, 2))
@@ -413,11 +440,14 @@ class HAB(nn.Module):
         y = self.norm1(x).view(B, H, W, C)
         conv = self.conv_block(y.permute(0, 3, 1, 2)).permute(0, 2, 3, 1).reshape(B, L, C)
         ws, sh = self.ws, self.shift
-        if sh:
-            y = torch.roll(y, (-sh, -sh), (1, 2))
-        a = _reverse(self.attn(_partition(y, ws), mask if sh else None), ws, B, H, W)
-        if sh:
-            a = torch.roll(a, (sh, sh), (1, 2))
+        if self.attn.fused_ok(x, hw, sh):
+            a = self.attn.forward_image(y.reshape(B, L, C), hw, sh)
+        else:
+            if sh:
+                y = torch.roll(y, (-sh, -sh), (1, 2))
+            a = _reverse(self.attn(_partition(y, ws), mask if sh else None), ws, B, H, W)
+            if sh:
+                a = torch.roll(a, (sh, sh), (1, 2))
         x = x + a.reshape(B, L, C) + conv * self.conv_scale
         return x + self.mlp(self.norm2(x))
 

@@ -15,7 +15,8 @@ from .dispatch import (  # noqa: F401
     backend_for, set_backend_override, native_required, NativeMissingError, stats, reset_stats, torch_reference,
 )
 from .core import (  # noqa: F401
-    linear, linear_geglu, attention, attention_lse, attention_kv2, attention_bias, group_norm, layer_norm, conv2d,
+    linear, linear_geglu, attention, attention_lse, attention_kv2, attention_bias, window_attention,
+    window_attention_domain, window_attention_enabled, group_norm, layer_norm, conv2d,
     conv2d_into, conv_slice_layout, conv_transpose2d, conv_transpose_phase_weights, silu, gelu, activation, ACT_CODES,
     upsample_nearest2x, timestep_embedding, cfg_combine, euler_step, depthwise_conv2d_nhwc,
     depthwise_conv2d_nhwc_lnstats,

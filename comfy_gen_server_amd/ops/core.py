@@ -680,6 +680,100 @@ def attention_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: torc
     return torch.softmax(s, -1).to(v.dtype) @ v
 
 
+# Fused shifted-window attention (csrc/kernels/window_attn.hip). CGS_WINDOW_ATTN=0 / 1 turns the models' use of it
+# off / on for every window size; unset, the per-window-size default measured in profiles/r14/window_attn.md holds.
+_WINDOW_ATTN_DEFAULT = {8: True, 16: True}
+_WIN_GEOM: dict = {}
+
+
+def window_attention_enabled(ws: int) -> bool:
+    env = os.environ.get("CGS_WINDOW_ATTN")
+    return _WINDOW_ATTN_DEFAULT.get(ws, False) if env is None else env == "1"
+
+
+def window_attention_domain(hw, ws: int, shift: int, heads: int, D: int) -> bool:
+    """The shapes cgs_window_attn_fwd takes (the device path also needs bf16 operands)."""
+    H, W = hw
+    return ws in (8, 16) and H % ws == 0 and W % ws == 0 and 0 <= shift < ws and D % 2 == 0 and 2 <= D <= 64 \
+        and heads > 0
+
+
+def _window_geometry(H: int, W: int, ws: int, shift: int, device):
+    """(rel index [N * N] into the (2ws-1)^2 table, shift mask [nW, N, N] of 0 / -100 or None), cached."""
+    key = (H, W, ws, shift, str(device))
+    g = _WIN_GEOM.get(key)
+    if g is None:
+        c = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")).flatten(1)
+        r = (c[:, :, None] - c[:, None, :]) + (ws - 1)
+        rel = (r[0] * (2 * ws - 1) + r[1]).reshape(-1).to(device)
+        mask = None
+        if shift:
+            def axis(n):
+                i = torch.arange(n)
+                return (i >= n - ws).long() + (i >= n - shift).long()
+            lab = 3 * axis(H)[:, None] + axis(W)[None, :]
+            win = lab.view(H // ws, ws, W // ws, ws).permute(0, 2, 1, 3).reshape(-1, ws * ws)
+            mask = torch.where(win[:, None, :] != win[:, :, None], -100.0, 0.0).to(device)
+        if len(_WIN_GEOM) > 64:
+            _WIN_GEOM.clear()
+        g = _WIN_GEOM[key] = (rel, mask)
+    return g
+
+
+def window_attention(qkv: torch.Tensor, hw, ws: int, shift: int, heads: int, table: torch.Tensor,
+                     scale: float | None = None, cosine: bool = False,
+                     head_scale: torch.Tensor | None = None) -> torch.Tensor:
+    """(Shifted-)window attention of the Swin-family upscalers on image-level tokens:
+
+        y = roll(x, (-shift, -shift)); per ws x ws window of y and head
+        softmax(scale * head_scale[h] * s + table[r(q, k), h] + m(q, k)) v       (fp32 scores and softmax)
+
+    ``qkv`` [B, H*W, 3*C]: the qkv projection of the un-rolled, un-partitioned tokens, channel order [3][heads][D];
+    returns [B, H*W, C] in the un-rolled token order, channel order [heads][D] (what ``proj`` consumes). ``table``
+    [(2ws-1)^2, heads] is the relative-position table, r = (yq - yk + ws-1) * (2ws-1) + (xq - xk + ws-1); m = -100
+    between tokens of different shift regions (``shift`` > 0). ``cosine``: s = cos(q, k) (SwinV2), the norms taken in
+    fp32 and applied to the fp32 scores; else s = q . k. bf16 on the GPU inside ``window_attention_domain``: one
+    launch of cgs_window_attn_fwd, which reads qkv in place and writes the result at the un-shifted pixels (no
+    roll, partition, pad, bias or mask tensor). Elsewhere: the same function composed from roll, partition,
+    ``attention_bias`` (table gather + shift mask), reverse and roll back -- fp32 on the CPU."""
+    B, L, C3 = qkv.shape
+    H, W = hw
+    C = C3 // 3
+    D = C // heads
+    scale = D ** -0.5 if scale is None else float(scale)
+    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and L == H * W and window_attention_domain(hw, ws, shift, heads, D)
+            and tuple(table.shape) == ((2 * ws - 1) ** 2, heads)
+            and backend_for("window_attention", qkv, "cgs_window_attn_fwd") == "hip"):
+        qkv = qkv.contiguous()
+        tab = table.float().contiguous()
+        hs = None if head_scale is None else head_scale.float().reshape(heads).contiguous()
+        o = torch.empty((B, L, C), device=qkv.device, dtype=qkv.dtype)
+        _check(_lib().cgs_window_attn_fwd(qkv.data_ptr(), o.data_ptr(), tab.data_ptr(), scale, 1 if cosine else 0,
+                                          _ptr(hs), B, H, W, heads, D, ws, shift, _stream()), "cgs_window_attn_fwd")
+        count("window_attention", "hip")
+        count("attention", "hip")
+        return o
+    if qkv.device.type == "cpu":
+        count("window_attention", "torch")
+    x = qkv.float() if qkv.device.type == "cpu" else qkv
+    y = x.reshape(B, H, W, C3)
+    if shift:
+        y = torch.roll(y, (-shift, -shift), (1, 2))
+    N = ws * ws
+    win = y.view(B, H // ws, ws, W // ws, ws, C3).permute(0, 1, 3, 2, 4, 5).reshape(-1, N, C3)
+    q, k, v = win.view(-1, N, 3, heads, D).permute(2, 0, 3, 1, 4).unbind(0)
+    if cosine:
+        q = F.normalize(q.float(), dim=-1).to(v.dtype)
+        k = F.normalize(k.float(), dim=-1).to(v.dtype)
+    rel, mask = _window_geometry(H, W, ws, shift, qkv.device)
+    bias = table.float()[rel].view(N, N, heads).permute(2, 0, 1)
+    o = attention_bias(q, k, v, bias, mask, scale=scale, head_scale=head_scale)
+    o = o.transpose(1, 2).reshape(B, H // ws, W // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
+    if shift:
+        o = torch.roll(o, (shift, shift), (1, 2))
+    return o.reshape(B, L, C).to(qkv.dtype)
+
+
 def attention_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int):
     """Unmasked attention plus the natural-log log-sum-exp of the scaled scores per (b, h, query):
     ``(o [B, Sq, H*D] in q's dtype, lse fp32 [B, H, Sq])`` -- the partial result of one K/V block
