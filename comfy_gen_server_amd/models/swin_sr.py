@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .layers import Conv2d, LayerNorm, Linear
+from .layers import Conv2d, LayerNorm, Linear, _hooked
 
 
 def _rel_index(ws: int) -> torch.Tensor:
@@ -65,6 +65,23 @@ def pad_to_multiple(x: torch.Tensor, m: int) -> torch.Tensor:
     return F.pad(x, (0, pw, 0, ph), "reflect" if ph < H and pw < W else "replicate")
 
 
+def _narrow_ok(x: torch.Tensor, *linears) -> bool:
+    """``ops.narrow_linear`` serves these Linear layers for x (``CGS_NARROW_LINEAR``): every K and N in its domain,
+    plain weights in x's dtype on x's device (hooked or cast-weight layers keep the composed path), and x on the CPU
+    (the fp32 composition) or bf16 on the device with the kernel."""
+    if not ops.narrow_linear_enabled():
+        return False
+    if any(_hooked(m) or m.weight.dtype != x.dtype or m.weight.device != x.device
+           or not ops.narrow_linear_domain(m.in_features, m.out_features) for m in linears):
+        return False
+    return x.device.type == "cpu" or (x.dtype == torch.bfloat16
+                                      and ops.backend_for("gemm", x, "cgs_gemm_narrow") == "hip")
+
+
+def _ln(norm: LayerNorm):
+    return norm.weight, norm.bias, norm.eps
+
+
 def _partition(x: torch.Tensor, ws: int) -> torch.Tensor:
     B, H, W, C = x.shape
     return x.view(B, H // ws, ws, W // ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws, C)
@@ -103,10 +120,21 @@ class WindowAttention(nn.Module):
         self.proj = Linear(dim, dim)
         self.register_buffer("rel_index", _rel_index(ws), persistent=False)
 
+    def _cpb(self) -> torch.Tensor:
+        """cpb_mlp(coords), [(2ws-1)^2, heads]. bf16 on the device with ``CGS_NARROW_LINEAR`` on: the K = 2 coordinate
+        layer runs on the narrow kernel, K zero-padded to 4 and the ReLU in its epilogue (no vendor GEMM)."""
+        l0, l2 = self.cpb_mlp[0], self.cpb_mlp[2]
+        coords = self.coords_table.to(l0.weight.dtype)
+        if (ops.narrow_linear_enabled() and coords.is_cuda and coords.dtype == torch.bfloat16 and not _hooked(l0)
+                and coords.device == l0.weight.device and ops.backend_for("gemm", coords, "cgs_gemm_narrow") == "hip"):
+            w4 = l0._derived_get("w_k4", lambda: F.pad(l0.weight, (0, 2)))
+            return l2(ops.narrow_linear(F.pad(coords, (0, 2)), w4, l0.bias, act="relu"))
+        return self.cpb_mlp(coords)
+
     def position_bias(self) -> torch.Tensor:
         """[heads, N, N] additive bias (fp32)."""
         if self.v2:
-            tab = self.cpb_mlp(self.coords_table.to(self.cpb_mlp[0].weight.dtype)).float()
+            tab = self._cpb().float()
             bias = 16 * torch.sigmoid(tab[self.rel_index.view(-1)])
         else:
             bias = self.relative_position_bias_table.float()[self.rel_index.view(-1)]
@@ -127,17 +155,30 @@ class WindowAttention(nn.Module):
         return x.device.type == "cpu" or (x.dtype == torch.bfloat16
                                           and ops.backend_for("window_attention", x, "cgs_window_attn_fwd") == "hip")
 
-    def forward_image(self, x: torch.Tensor, hw, shift: int) -> torch.Tensor:
+    def _qkv_narrow(self, x: torch.Tensor, ln) -> torch.Tensor:
+        """The qkv projection on ``ops.narrow_linear``: ``ln`` (a preceding LayerNorm) folded in; SwinV2's q / v bias
+        is the kernel's bias, cat([q_bias, 0, v_bias]) cached with the layer's derived tensors."""
+        bias = self.qkv.bias
+        if self.v2 and self.q_bias is not None:
+            bias = self.qkv._derived_get(f"qv_bias {x.device} {x.dtype}", lambda: torch.cat(
+                [self.q_bias, torch.zeros_like(self.v_bias), self.v_bias]).to(device=x.device, dtype=x.dtype))
+        return ops.narrow_linear(x, self.qkv.weight, bias, ln=ln)
+
+    def forward_image(self, x: torch.Tensor, hw, shift: int, narrow: bool = False, ln=None,
+                      residual: torch.Tensor | None = None) -> torch.Tensor:
         """Tokens [B, H*W, C] of the whole image, un-rolled and un-partitioned: the qkv projection is per token, so
-        it runs where the tokens lie and ``ops.window_attention`` does the shift, the windows and the score terms."""
+        it runs where the tokens lie and ``ops.window_attention`` does the shift, the windows and the score terms.
+        ``narrow`` (the caller checked ``_narrow_ok``): qkv of ``ln``(x) in one ``ops.narrow_linear`` launch and
+        ``residual`` added in proj's epilogue."""
+        qkv = self._qkv_narrow(x, ln) if narrow else self._qkv(x)
         if self.v2:
-            table = 16 * torch.sigmoid(self.cpb_mlp(self.coords_table.to(self.cpb_mlp[0].weight.dtype)).float())
-            o = ops.window_attention(self._qkv(x), hw, self.ws, shift, self.heads, table, scale=1.0, cosine=True,
+            table = 16 * torch.sigmoid(self._cpb().float())
+            o = ops.window_attention(qkv, hw, self.ws, shift, self.heads, table, scale=1.0, cosine=True,
                                      head_scale=torch.clamp(self.logit_scale.float(), max=math.log(100.0)).exp())
         else:
-            o = ops.window_attention(self._qkv(x), hw, self.ws, shift, self.heads,
+            o = ops.window_attention(qkv, hw, self.ws, shift, self.heads,
                                      self.relative_position_bias_table.float(), scale=self.scale)
-        return self.proj(o)
+        return ops.narrow_linear(o, self.proj.weight, self.proj.bias, residual=residual) if narrow else self.proj(o)
 
     def forward(self, x: torch.Tensor, mask: torch.Tensor | None) -> torch.Tensor:
         Bw, N, C = x.shape
@@ -162,6 +203,12 @@ class _Mlp(nn.Module):
 
     def forward(self, x):
         return self.fc2(F.gelu(self.fc1(x)))
+
+    def narrow(self, x, ln=None, residual=None):
+        """fc2(gelu(fc1(ln(x)))) + residual in two ``ops.narrow_linear`` launches: the LayerNorm and the GELU in
+        fc1's kernel, the residual in fc2's epilogue."""
+        h = ops.narrow_linear(x, self.fc1.weight, self.fc1.bias, ln=ln, act="gelu")
+        return ops.narrow_linear(h, self.fc2.weight, self.fc2.bias, residual=residual)
 
 
 class SwinBlock(nn.Module):
@@ -193,6 +240,13 @@ class SwinBlock(nn.Module):
         return y.reshape(B, L, C)
 
     def forward(self, x, hw):
+        at, mlp = self.attn, self.mlp
+        if at.fused_ok(x, hw, self.shift) and _narrow_ok(x, at.qkv, at.proj, mlp.fc1, mlp.fc2):
+            if self.v2:      # res-post-norm: the residual is added by the row LayerNorm
+                x = ops.layer_norm(at.forward_image(x, hw, self.shift, narrow=True), *_ln(self.norm1), residual=x)
+                return ops.layer_norm(mlp.narrow(x), *_ln(self.norm2), residual=x)
+            x = at.forward_image(x, hw, self.shift, narrow=True, ln=_ln(self.norm1), residual=x)
+            return mlp.narrow(x, ln=_ln(self.norm2), residual=x)
         if self.v2:
             x = x + self.norm1(self._attend(x, hw))
             return x + self.norm2(self.mlp(x))
@@ -440,6 +494,10 @@ class HAB(nn.Module):
         y = self.norm1(x).view(B, H, W, C)
         conv = self.conv_block(y.permute(0, 3, 1, 2)).permute(0, 2, 3, 1).reshape(B, L, C)
         ws, sh = self.ws, self.shift
+        if self.attn.fused_ok(x, hw, sh) and _narrow_ok(x, self.attn.qkv, self.attn.proj, self.mlp.fc1, self.mlp.fc2):
+            # (norm1(x) exists for the conv branch, so qkv reads it; the block's residual rides on proj and fc2)
+            x = self.attn.forward_image(y.reshape(B, L, C), hw, sh, narrow=True, residual=x) + conv * self.conv_scale
+            return self.mlp.narrow(x, ln=_ln(self.norm2), residual=x)
         if self.attn.fused_ok(x, hw, sh):
             a = self.attn.forward_image(y.reshape(B, L, C), hw, sh)
         else:
@@ -481,7 +539,11 @@ class OCAB(nn.Module):
         H, W = hw
         B, L, C = x.shape
         ws, ows, h = self.ws, self.ows, self.heads
-        qkv = self.qkv(self.norm1(x)).view(B, H, W, 3, C)
+        narrow = _narrow_ok(x, self.qkv, self.proj, self.mlp.fc1, self.mlp.fc2)
+        if narrow:
+            qkv = ops.narrow_linear(x, self.qkv.weight, self.qkv.bias, ln=_ln(self.norm1)).view(B, H, W, 3, C)
+        else:
+            qkv = self.qkv(self.norm1(x)).view(B, H, W, 3, C)
         q = _partition(qkv[..., 0, :], ws)                                   # [B*nW, ws*ws, C]
         kv = qkv[..., 1:, :].reshape(B, H, W, 2 * C).permute(0, 3, 1, 2)     # [B, 2C, H, W]
         kv = F.unfold(kv, ows, stride=ws, padding=(ows - ws) // 2)            # [B, 2C*ows*ows, nW]
@@ -494,6 +556,9 @@ class OCAB(nn.Module):
         bias = self.relative_position_bias_table.float()[self.rel_index.reshape(-1)]
         bias = bias.view(ws * ws, ows * ows, h).permute(2, 0, 1)
         o = ops.attention_bias(qh, kh, vh, bias, scale=self.scale).transpose(1, 2).reshape(-1, ws * ws, C)
+        if narrow:
+            x = ops.narrow_linear(_reverse(o, ws, B, H, W).reshape(B, L, C), self.proj.weight, self.proj.bias, residual=x)
+            return self.mlp.narrow(x, ln=_ln(self.norm2), residual=x)
         x = self.proj(_reverse(o, ws, B, H, W).reshape(B, L, C)) + x
         return x + self.mlp(self.norm2(x))
 

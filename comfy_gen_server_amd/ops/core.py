@@ -298,6 +298,10 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
             # on the hook-free transformer path, where y is never modified in place)
             y._cgs_rowpart = (rs_part[0], y.data_ptr())
         return y
+    if (be == "hip" and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and narrow_linear_enabled()
+            and narrow_linear_domain(x.shape[-1], weight.shape[0]) and _native.has_kernel("cgs_gemm_narrow")):
+        y = narrow_linear(x, weight, bias, act=act, residual=residual)       # K % 8 != 0: dim 180 / 60 (gemm_narrow.hip)
+        return y if out is None else out.view(y.shape).copy_(y)
     if be == "torch":
         count("gemm", "torch")
     else:
@@ -774,6 +778,86 @@ def window_attention(qkv: torch.Tensor, hw, ws: int, shift: int, heads: int, tab
     return o.reshape(B, L, C).to(qkv.dtype)
 
 
+# Narrow-K linear with fused LayerNorm and the row LayerNorm for C % 8 != 0 (csrc/kernels/gemm_narrow.hip).
+# CGS_NARROW_LINEAR=0 / 1 turns the routing of ``linear`` / ``layer_norm`` and the models' fused blocks off / on;
+# unset, the default measured in profiles/r15/narrow_linear.md holds.
+_NARROW_LINEAR_DEFAULT = True
+
+
+def narrow_linear_enabled() -> bool:
+    env = os.environ.get("CGS_NARROW_LINEAR")
+    return _NARROW_LINEAR_DEFAULT if env is None else env == "1"
+
+
+def narrow_linear_domain(K: int, N: int) -> bool:
+    """The shapes cgs_gemm_narrow takes (the device path also needs bf16 operands)."""
+    return 4 <= K <= 384 and K % 4 == 0 and N > 0 and N % 4 == 0
+
+
+def _param_for(p, x):
+    """A weight / bias / LayerNorm parameter as the kernels read it: x's device and dtype, contiguous, 8-byte aligned
+    (cast as ``layer_norm`` casts, each on its own)."""
+    if p is None:
+        return None
+    if p.dtype != x.dtype or p.device != x.device or not p.is_contiguous():
+        p = p.to(device=x.device, dtype=x.dtype).contiguous()
+    return p if p.data_ptr() % 8 == 0 else p.clone()
+
+
+def _rows4(t, cols):
+    """[rows, cols] view of t with unit column stride, a row pitch that is a multiple of 4 and an 8-byte aligned
+    base (one ``.contiguous()`` where needed), and that pitch."""
+    t = t.reshape(-1, cols)
+    if t.stride(-1) != 1 or (t.shape[0] > 1 and (t.stride(0) < cols or t.stride(0) % 4)) or t.data_ptr() % 8:
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else cols)
+
+
+def narrow_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, ln=None,
+                  act: str | None = None, residual: torch.Tensor | None = None) -> torch.Tensor:
+    """y = act(LN(x) @ weight^T (+ bias)) (+ residual) for narrow rows, 4 <= K <= 384 with K % 4 == 0 (the dim-180 /
+    dim-60 Swin-family blocks, whose K fails the 16-byte rules of the tiled GEMMs). ``ln`` = (gamma, beta, eps), each
+    of gamma / beta optional, or None for no LayerNorm; ``act`` as in ``linear``, applied before the residual.
+    bf16 on the GPU inside ``narrow_linear_domain``: one launch of cgs_gemm_narrow, which keeps the whole K of a row
+    tile resident, normalises the staged rows in place (LN(x) never reaches memory) and adds bias, activation and
+    residual in its epilogue. Elsewhere on the device: ``layer_norm`` then ``linear``. CPU: the fp32 torch
+    composition F.layer_norm -> F.linear -> activation -> add."""
+    assert act is None or (act in ACT_CODES and act != "leaky_relu"), act
+    K, N = x.shape[-1], weight.shape[0]
+    if x.device.type == "cpu" or backend_for("gemm", x, "cgs_gemm_narrow") == "torch":
+        count("gemm", "torch")
+        y = x.float()
+        if ln is not None:
+            g, b, eps = ln
+            y = F.layer_norm(y, (K,), None if g is None else g.float(), None if b is None else b.float(), eps)
+        y = F.linear(y, weight.float(), None if bias is None else bias.float())
+        if act is not None:
+            y = _act_torch(y, act)
+        if residual is not None:
+            y = y + residual.float()
+        return y.to(x.dtype)
+    if not (x.dtype == torch.bfloat16 and narrow_linear_domain(K, N)):
+        if ln is not None:
+            x = layer_norm(x, ln[0], ln[1], ln[2])
+        return linear(x, weight.to(x.dtype), None if bias is None else bias.to(x.dtype), residual=residual, act=act)
+    a, lda = _rows4(x, K)
+    M = a.shape[0]
+    w, bv = _param_for(weight, x), _param_for(bias, x)
+    g, b, eps = (None, None, 0.0) if ln is None else (_param_for(ln[0], x), _param_for(ln[1], x), float(ln[2]))
+    r, ldr = (None, 0) if residual is None else _rows4(residual.to(x.dtype), N)
+    y = torch.empty((M, N), device=x.device, dtype=x.dtype)
+    if M:
+        _check(_lib().cgs_gemm_narrow(a.data_ptr(), lda, w.data_ptr(), _ptr(bv), _ptr(g), _ptr(b), eps,
+                                      0 if ln is None else 1, _ptr(r), ldr, y.data_ptr(), N, M, N, K,
+                                      0 if act is None else ACT_CODES[act], _stream()), "cgs_gemm_narrow")
+    count("gemm", "hip")
+    if act is not None:
+        count("act_fused", "hip")
+    if ln is not None:
+        count("layernorm_fused", "hip")
+    return y.view(*x.shape[:-1], N)
+
+
 def attention_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int):
     """Unmasked attention plus the natural-log log-sum-exp of the scaled scores per (b, h, query):
     ``(o [B, Sq, H*D] in q's dtype, lse fp32 [B, H, Sq])`` -- the partial result of one K/V block
@@ -1020,7 +1104,16 @@ def group_norm(x: torch.Tensor, groups: int, weight: torch.Tensor | None, bias: 
 
 
 def layer_norm(x: torch.Tensor, weight: torch.Tensor | None, bias: torch.Tensor | None,
-               eps: float = 1e-5) -> torch.Tensor:
+               eps: float = 1e-5, residual: torch.Tensor | None = None) -> torch.Tensor:
+    """LayerNorm over the last dim. ``residual`` (x's shape): y = LN(x) + residual -- one pass on the row kernel for
+    C % 8 != 0 (cgs_layernorm_rows4, bf16, C % 4 == 0, C <= 1024, behind ``narrow_linear_enabled``), an addition after
+    the LayerNorm elsewhere."""
+    if residual is not None:
+        C = x.shape[-1]
+        if (x.is_cuda and x.dtype == torch.bfloat16 and C % 8 and C % 4 == 0 and C <= 1024 and narrow_linear_enabled()
+                and backend_for("layernorm", x, "cgs_layernorm_rows4") == "hip"):
+            return _layer_norm_rows4(x, weight, bias, eps, residual)
+        return layer_norm(x, weight, bias, eps) + residual
     be = backend_for("layernorm", x, "cgs_layernorm")
     C = x.shape[-1]
     if be == "hip" and x.dtype == torch.float32 and _f32.available("cgs_layernorm_f32"):
@@ -1042,12 +1135,35 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor | None, bias: torch.Tensor 
         _check(_lib().cgs_layernorm(xc.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(bias),
                                     rows, C, float(eps), _DT[x.dtype], _stream()), "cgs_layernorm")
         return y
+    if (be == "hip" and x.dtype == torch.bfloat16 and C % 4 == 0 and C <= 1024 and narrow_linear_enabled()
+            and _native.has_kernel("cgs_layernorm_rows4")):
+        return _layer_norm_rows4(x, weight, bias, eps, None)
     if x.device.type == "cpu":
         count("layernorm", "torch")
     else:
         vendor_fallback("layernorm", f"dtype {x.dtype}, C={C}")
     return F.layer_norm(x.float(), (C,), None if weight is None else weight.float(),
                         None if bias is None else bias.float(), eps).to(x.dtype)
+
+
+def _layer_norm_rows4(x, weight, bias, eps, residual):
+    """bf16 rows of C % 4 == 0, C <= 1024 values on cgs_layernorm_rows4 (8-byte loads), ``residual`` added in fp32
+    before the one rounding."""
+    C = x.shape[-1]
+    xc = x.contiguous()
+    xc = xc if xc.data_ptr() % 8 == 0 else xc.clone()
+    r = None
+    if residual is not None:
+        r = residual.to(x.dtype).expand_as(x).contiguous()
+        r = r if r.data_ptr() % 8 == 0 else r.clone()
+    y = torch.empty_like(xc)
+    rows = xc.numel() // C
+    if rows:
+        _check(_lib().cgs_layernorm_rows4(xc.data_ptr(), y.data_ptr(), _ptr(_param_for(weight, x)),
+                                          _ptr(_param_for(bias, x)), _ptr(r), rows, C, float(eps), _stream()),
+               "cgs_layernorm_rows4")
+    count("layernorm", "hip")
+    return y
 
 
 # ----------------------------------------------------------------------------------------------
