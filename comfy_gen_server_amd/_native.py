@@ -95,6 +95,9 @@ KERNEL_SIGNATURES = {
     # fused shifted-window attention (window_attn.hip): qkv [B, H*W, 3C], o [B, H*W, C], table [(2ws-1)^2, heads],
     # scale, cosine, hscale [heads] or null, B, H, W, heads, D, ws, shift, stream
     "cgs_window_attn_fwd": [_P, _P, _P, _F, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    # fused overlapping cross-attention, HAT's OCAB (overlap_attn.hip): qkv [B, H*W, 3C], o [B, H*W, C], table
+    # [(ws+ows-1)^2, heads], scale, B, H, W, heads, D, ws, ows, stream
+    "cgs_overlap_attn_fwd": [_P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _P],
     # narrow-K linear with optional fused LayerNorm (gemm_narrow.hip): x, lda, w, bias, gamma, beta, eps, ln, res, ldr,
     # y, ldc, M, N, K, CgsAct code, stream; row LayerNorm for C % 4 == 0: x, y, w, b, res, rows, C, eps, stream
     "cgs_gemm_narrow": [_P, _L, _P, _P, _P, _P, _F, _I, _P, _L, _P, _L, _L, _I, _I, _I, _P],

@@ -6,7 +6,8 @@ residual Swin transformer blocks, and every upsampler head the reference detects
 
 Layout: activations stay token-major ``[B, H*W, C]`` between blocks. SwinIR / Swin2SR / HAT blocks with 8 x 8 or
 16 x 16 windows project qkv where the tokens lie and call ``ops.window_attention`` (``CGS_WINDOW_ATTN``), whose
-kernel does the cyclic shift, the windows, the position bias and the shift mask in its addressing; elsewhere a
+kernel does the cyclic shift, the windows, the position bias and the shift mask in its addressing; HAT's overlapping
+cross-attention calls ``ops.overlap_attention`` (``CGS_OVERLAP_ATTN``) on the same packed qkv; elsewhere a
 block rolls and partitions the ``[B, H, W, C]`` view into ``ws x ws`` windows, runs one batched attention over
 ``B * nW`` windows (fp32 softmax), and reverses. Linear layers are ``layers.Linear`` (HIP GEMM
 on the device), convs are ``layers.Conv2d`` (NHWC implicit-GEMM MFMA kernel). The relative
@@ -535,31 +536,25 @@ class OCAB(nn.Module):
         self.mlp = _Mlp(dim, int(dim * mlp_ratio))
         self.register_buffer("rel_index", _rel_index_oca(ws, self.ows), persistent=False)
 
+    def fused_ok(self, x: torch.Tensor, hw) -> bool:
+        """The fused kernel serves these tokens: the switch is on for this window size, the shapes are in
+        ``ops.overlap_attention``'s device domain and x is bf16 on the device with the kernel."""
+        return (ops.overlap_attention_enabled(self.ws) and x.is_cuda and x.dtype == torch.bfloat16
+                and ops.overlap_attention_domain(hw, self.ws, self.ows, self.heads, self.dim // self.heads)
+                and ops.backend_for("overlap_attention", x, "cgs_overlap_attn_fwd") == "hip")
+
+    def attend(self, qkv: torch.Tensor, hw) -> torch.Tensor:
+        """qkv [B, H*W, 3C] where the tokens lie -> [B, H*W, C]: one fused launch (``fused_ok``), else the
+        composition (unfold, table gather, ``ops.attention_bias``) inside the op."""
+        return ops.overlap_attention(qkv, hw, self.ws, self.ows, self.heads, self.relative_position_bias_table.float(),
+                                     scale=self.scale, fused=self.fused_ok(qkv, hw))
+
     def forward(self, x, hw):
-        H, W = hw
-        B, L, C = x.shape
-        ws, ows, h = self.ws, self.ows, self.heads
-        narrow = _narrow_ok(x, self.qkv, self.proj, self.mlp.fc1, self.mlp.fc2)
-        if narrow:
-            qkv = ops.narrow_linear(x, self.qkv.weight, self.qkv.bias, ln=_ln(self.norm1)).view(B, H, W, 3, C)
-        else:
-            qkv = self.qkv(self.norm1(x)).view(B, H, W, 3, C)
-        q = _partition(qkv[..., 0, :], ws)                                   # [B*nW, ws*ws, C]
-        kv = qkv[..., 1:, :].reshape(B, H, W, 2 * C).permute(0, 3, 1, 2)     # [B, 2C, H, W]
-        kv = F.unfold(kv, ows, stride=ws, padding=(ows - ws) // 2)            # [B, 2C*ows*ows, nW]
-        nW = kv.shape[-1]
-        kv = kv.view(B, 2, C, ows * ows, nW).permute(1, 0, 4, 3, 2).reshape(2, B * nW, ows * ows, C)
-        d = C // h
-        qh = q.view(-1, ws * ws, h, d).transpose(1, 2)
-        kh = kv[0].view(-1, ows * ows, h, d).transpose(1, 2)
-        vh = kv[1].view(-1, ows * ows, h, d).transpose(1, 2)
-        bias = self.relative_position_bias_table.float()[self.rel_index.reshape(-1)]
-        bias = bias.view(ws * ws, ows * ows, h).permute(2, 0, 1)
-        o = ops.attention_bias(qh, kh, vh, bias, scale=self.scale).transpose(1, 2).reshape(-1, ws * ws, C)
-        if narrow:
-            x = ops.narrow_linear(_reverse(o, ws, B, H, W).reshape(B, L, C), self.proj.weight, self.proj.bias, residual=x)
+        if _narrow_ok(x, self.qkv, self.proj, self.mlp.fc1, self.mlp.fc2):
+            qkv = ops.narrow_linear(x, self.qkv.weight, self.qkv.bias, ln=_ln(self.norm1))
+            x = ops.narrow_linear(self.attend(qkv, hw), self.proj.weight, self.proj.bias, residual=x)
             return self.mlp.narrow(x, ln=_ln(self.norm2), residual=x)
-        x = self.proj(_reverse(o, ws, B, H, W).reshape(B, L, C)) + x
+        x = self.proj(self.attend(self.qkv(self.norm1(x)), hw)) + x
         return x + self.mlp(self.norm2(x))
 
 

@@ -3076,3 +3076,82 @@ def vae_out_u8(x: torch.Tensor) -> torch.Tensor:
     count("vae_u8", "torch")
     v = torch.clamp((x.float() + 1.0) / 2.0, 0.0, 1.0).movedim(1, -1)
     return (v * 255.0 + 0.5).to(torch.uint8)
+
+
+# Fused overlapping cross-attention, HAT's OCAB (csrc/kernels/overlap_attn.hip). CGS_OVERLAP_ATTN=0 / 1 turns the
+# model's use of it off / on for every window size; unset, the per-window-size default measured in
+# profiles/r16/overlap_attn.md holds.
+_OVERLAP_ATTN_DEFAULT = {8: True, 16: True}
+_OVERLAP_GEOM: dict = {}
+
+
+def overlap_attention_enabled(ws: int) -> bool:
+    env = os.environ.get("CGS_OVERLAP_ATTN")
+    return _OVERLAP_ATTN_DEFAULT.get(ws, False) if env is None else env == "1"
+
+
+def overlap_attention_domain(hw, ws: int, ows: int, heads: int, D: int) -> bool:
+    """The shapes cgs_overlap_attn_fwd takes (the device path also needs bf16 operands)."""
+    H, W = hw
+    return (ws, ows) in ((8, 12), (16, 24)) and H % ws == 0 and W % ws == 0 and D % 2 == 0 and 2 <= D <= 32 \
+        and heads > 0
+
+
+def _overlap_rel_index(ws: int, ows: int, device) -> torch.Tensor:
+    """[ws*ws * ows*ows] index into the (ws+ows-1)^2 table, negative values wrapped from the end; cached."""
+    key = (ws, ows, str(device))
+    rel = _OVERLAP_GEOM.get(key)
+    if rel is None:
+        def grid(n):
+            return torch.stack(torch.meshgrid(torch.arange(n), torch.arange(n), indexing="ij")).flatten(1)
+        r = (grid(ows)[:, None, :] - grid(ws)[:, :, None]).permute(1, 2, 0) + (ws - ows + 1)
+        T = ws + ows - 1
+        rel = _OVERLAP_GEOM[key] = ((r[..., 0] * T + r[..., 1]) % (T * T)).reshape(-1).to(device)
+    return rel
+
+
+def overlap_attention(qkv: torch.Tensor, hw, ws: int, ows: int, heads: int, table: torch.Tensor,
+                      scale: float | None = None, fused: bool = True) -> torch.Tensor:
+    """Overlapping cross-attention of HAT (OCAB) on image-level tokens: per ws x ws window and head
+
+        softmax_k(scale * q . k + table[r(q, k), h]) v       (fp32 scores and softmax)
+
+    over the ows x ows positions around the window, (wy ws - pad + ky, wx ws - pad + kx) with pad = (ows - ws) / 2.
+    A position outside the image has k = v = 0 and is not masked (``nn.Unfold(padding=pad)``). r = a (ws+ows-1) + b
+    with a = ky - qy + (ws - ows + 1), b likewise; negative r index ``table`` [(ws+ows-1)^2, heads] from the end.
+    ``qkv`` [B, H*W, 3*C], channel order [3][heads][D]; returns [B, H*W, C] in token order, channel order [heads][D].
+    bf16 on the GPU inside ``overlap_attention_domain``: one launch of cgs_overlap_attn_fwd, which reads qkv in place
+    (no slice, unfold, partition, bias or pad tensor). Elsewhere, and with ``fused`` False (the model's switch,
+    ``overlap_attention_enabled``, off): the same function composed from ``F.unfold``, the table gather and
+    ``attention_bias``."""
+    B, L, C3 = qkv.shape
+    H, W = hw
+    C = C3 // 3
+    D = C // heads
+    scale = D ** -0.5 if scale is None else float(scale)
+    T = ws + ows - 1
+    if (fused and qkv.is_cuda and qkv.dtype == torch.bfloat16 and L == H * W and overlap_attention_domain(hw, ws, ows, heads, D)
+            and tuple(table.shape) == (T * T, heads)
+            and backend_for("overlap_attention", qkv, "cgs_overlap_attn_fwd") == "hip"):
+        qkv = qkv.contiguous()
+        tab = table.float().contiguous()
+        o = torch.empty((B, L, C), device=qkv.device, dtype=qkv.dtype)
+        _check(_lib().cgs_overlap_attn_fwd(qkv.data_ptr(), o.data_ptr(), tab.data_ptr(), scale, B, H, W, heads, D,
+                                           ws, ows, _stream()), "cgs_overlap_attn_fwd")
+        count("overlap_attention", "hip")
+        count("attention", "hip")
+        return o
+    if qkv.device.type == "cpu":
+        count("overlap_attention", "torch")
+    y = qkv.reshape(B, H, W, 3, C)
+    q = y[..., 0, :].reshape(B, H // ws, ws, W // ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws, C)
+    kv = y[..., 1:, :].reshape(B, H, W, 2 * C).permute(0, 3, 1, 2)         # [B, 2C, H, W]
+    kv = F.unfold(kv, ows, stride=ws, padding=(ows - ws) // 2)              # [B, 2C*ows*ows, nW]
+    nW = kv.shape[-1]
+    kv = kv.view(B, 2, C, ows * ows, nW).permute(1, 0, 4, 3, 2).reshape(2, B * nW, ows * ows, C)
+    qh = q.view(-1, ws * ws, heads, D).transpose(1, 2)
+    kh = kv[0].view(-1, ows * ows, heads, D).transpose(1, 2)
+    vh = kv[1].view(-1, ows * ows, heads, D).transpose(1, 2)
+    bias = table.float()[_overlap_rel_index(ws, ows, qkv.device)].view(ws * ws, ows * ows, heads).permute(2, 0, 1)
+    o = attention_bias(qh, kh, vh, bias, scale=scale).transpose(1, 2).reshape(-1, ws * ws, C)
+    return o.view(B, H // ws, W // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, L, C)
