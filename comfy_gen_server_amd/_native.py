@@ -98,6 +98,11 @@ KERNEL_SIGNATURES = {
     # fused overlapping cross-attention, HAT's OCAB (overlap_attn.hip): qkv [B, H*W, 3C], o [B, H*W, C], table
     # [(ws+ows-1)^2, heads], scale, B, H, W, heads, D, ws, ows, stream
     "cgs_overlap_attn_fwd": [_P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _P],
+    # channel (transposed) attention of DAT (channel_attn.hip): qkv [B, N, 3C], o [B, N, C], temperature fp32 [heads],
+    # ws, ws bytes, B, N, heads, D, stream; workspace bytes and the gram kernel's chunk length for (B, N, heads, D)
+    "cgs_channel_attn_fwd": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "cgs_channel_attn_ws_bytes": [_I, _I, _I, _I],
+    "cgs_channel_attn_chunk": [_I, _I, _I, _I],
     # narrow-K linear with optional fused LayerNorm (gemm_narrow.hip): x, lda, w, bias, gamma, beta, eps, ln, res, ldr,
     # y, ldc, M, N, K, CgsAct code, stream; row LayerNorm for C % 4 == 0: x, y, w, b, res, rows, C, eps, stream
     "cgs_gemm_narrow": [_P, _L, _P, _P, _P, _P, _F, _I, _P, _L, _P, _L, _L, _I, _I, _I, _P],
@@ -268,7 +273,7 @@ KERNEL_SIGNATURES = {
 }
 
 
-_RESTYPE = {"cgs_groupnorm_workspace": ctypes.c_longlong, "cgs_splitk_ws_bytes": ctypes.c_longlong, "cgs_groupnorm_f32_ws": ctypes.c_longlong, "cgs_grn_slices": ctypes.c_int, "cgs_v7_ws_bytes": ctypes.c_longlong, "cgs_gemm_skinny_ws_bytes": ctypes.c_longlong, "cgs_gemm_set_variant": None, "cgs_v7_set_dbg": None, "cgs_v6_set_mode": None, "cgs_attn_set_prio": None, "cgs_gn_set_blocks": None, "cgs_conv_smalln_set_lds": None, "cgs_attn_set_kv2_rows": None, "cgs_grn_set_rows": None,
+_RESTYPE = {"cgs_channel_attn_ws_bytes": ctypes.c_longlong, "cgs_groupnorm_workspace": ctypes.c_longlong, "cgs_splitk_ws_bytes": ctypes.c_longlong, "cgs_groupnorm_f32_ws": ctypes.c_longlong, "cgs_grn_slices": ctypes.c_int, "cgs_v7_ws_bytes": ctypes.c_longlong, "cgs_gemm_skinny_ws_bytes": ctypes.c_longlong, "cgs_gemm_set_variant": None, "cgs_v7_set_dbg": None, "cgs_v6_set_mode": None, "cgs_attn_set_prio": None, "cgs_gn_set_blocks": None, "cgs_conv_smalln_set_lds": None, "cgs_attn_set_kv2_rows": None, "cgs_grn_set_rows": None,
             "cgs_conv_set_variant": None, "cgs_set_tile_group": None, "cgs_conv_set_tile_group": None, "cgs_dwconv_set_px": None, "cgs_upconv_set_tile_group": None,
             "cgs_attn_set_variant": None,
             "cgs_conv_v6_set_loader": None}

@@ -5,8 +5,9 @@ architecture/DAT.py:897-1182``). Residual groups alternate two block kinds:
   (``split_size`` and its transpose) with a dynamic (MLP-generated) relative position bias and
   periodic half-window shifts; a depthwise-conv branch on V is mixed in through the adaptive
   interaction module (channel map from the conv branch, spatial map from the attention branch);
-* channel blocks: transposed (d x d) attention per head with a learned temperature, mixed with
-  the same conv branch the other way round;
+* channel blocks: transposed (d x d) attention per head with a learned temperature
+  (``ops.channel_attention`` on the packed qkv, ``CGS_CHANNEL_ATTN``), mixed with the same conv
+  branch the other way round;
 
 each followed by the spatial-gate feed-forward (SGFN). Projections are ``layers.Linear``, dense
 convs ``layers.Conv2d``; depthwise convs and BatchNorm stay on torch modules. Shift masks and
@@ -155,10 +156,9 @@ class AdaptiveChannelAttention(nn.Module):
     def forward(self, x, H, W):
         B, N, C = x.shape
         h = self.heads
-        q, k, v = self.qkv(x).view(B, N, 3, h, C // h).permute(2, 0, 3, 4, 1).unbind(0)   # [B, h, d, N]
-        s = F.normalize(q.float(), dim=-1) @ F.normalize(k.float(), dim=-1).transpose(-2, -1)
-        att = (torch.softmax(s * self.temperature.float(), -1).to(v.dtype) @ v)      # [B, h, d, N]
-        att = att.permute(0, 3, 1, 2).reshape(B, N, C)
+        qkv = self.qkv(x)
+        att = ops.channel_attention(qkv, h, self.temperature, fused=ops.channel_attention_enabled())
+        v = qkv.view(B, N, 3, h, C // h)[:, :, 2].permute(0, 2, 3, 1)                # [B, h, d, N]
         conv = self.dwconv(v.reshape(B, C, H, W))
         cmap = self.channel_interaction(_to_img(att, (H, W)))
         smap = self.spatial_interaction(conv).flatten(2).transpose(1, 2)             # [B, N, 1]

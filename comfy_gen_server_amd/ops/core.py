@@ -3155,3 +3155,53 @@ def overlap_attention(qkv: torch.Tensor, hw, ws: int, ows: int, heads: int, tabl
     bias = table.float()[_overlap_rel_index(ws, ows, qkv.device)].view(ws * ws, ows * ows, heads).permute(2, 0, 1)
     o = attention_bias(qh, kh, vh, bias, scale=scale).transpose(1, 2).reshape(-1, ws * ws, C)
     return o.view(B, H // ws, W // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, L, C)
+
+
+# Channel (transposed) attention of DAT's channel blocks (csrc/kernels/channel_attn.hip). CGS_CHANNEL_ATTN=0 / 1 turns
+# the model's use of it off / on; unset, the default measured in profiles/r17/channel_attn.md holds.
+_CHANNEL_ATTN_DEFAULT = True
+
+
+def channel_attention_enabled() -> bool:
+    env = os.environ.get("CGS_CHANNEL_ATTN")
+    return _CHANNEL_ATTN_DEFAULT if env is None else env == "1"
+
+
+def channel_attention_domain(heads: int, D: int) -> bool:
+    """The shapes cgs_channel_attn_fwd takes (the device path also needs bf16 operands)."""
+    return D % 2 == 0 and 2 <= D <= 32 and heads >= 1
+
+
+def channel_attention(qkv: torch.Tensor, heads: int, temperature: torch.Tensor, fused: bool = True) -> torch.Tensor:
+    """Channel attention of DAT on token-major qkv: per image and head, with q, k, v the [N, D] slices,
+
+        P = softmax_j(temperature[h] * cos(q[:, i], k[:, j]))  (fp32, D x D),      o[n, i] = sum_j P[i, j] v[n, j]
+
+    where cos normalises every channel over the N tokens as ``F.normalize`` does (eps 1e-12). ``qkv`` [B, N, 3*C],
+    channel order [3][heads][D]; ``temperature`` [heads] or [heads, 1, 1]; returns [B, N, C], channel order [heads][D].
+    bf16 on the GPU inside ``channel_attention_domain``: three launches of cgs_channel_attn_fwd, which reads qkv in
+    place (no fp32 copy, permute or normalised tensor). Elsewhere, and with ``fused`` False (the model's switch,
+    ``channel_attention_enabled``, off): the same function composed from ``F.normalize``, two matmuls and a softmax."""
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    if (fused and qkv.is_cuda and qkv.dtype == torch.bfloat16 and B > 0 and N > 0 and channel_attention_domain(heads, D)
+            and temperature.numel() == heads
+            and backend_for("channel_attention", qkv, "cgs_channel_attn_fwd") == "hip"):
+        qkv = qkv.contiguous()
+        t = temperature.detach().float().reshape(heads).contiguous()
+        nbytes = int(_lib().cgs_channel_attn_ws_bytes(B, N, heads, D))
+        if nbytes > 0:
+            ws = torch.empty(nbytes, device=qkv.device, dtype=torch.uint8)
+            o = torch.empty((B, N, C), device=qkv.device, dtype=qkv.dtype)
+            _check(_lib().cgs_channel_attn_fwd(qkv.data_ptr(), o.data_ptr(), t.data_ptr(), ws.data_ptr(), nbytes, B, N,
+                                               heads, D, _stream()), "cgs_channel_attn_fwd")
+            count("channel_attention", "hip")
+            count("attention", "hip")
+            return o
+    if qkv.device.type == "cpu":
+        count("channel_attention", "torch")
+    q, k, v = qkv.view(B, N, 3, heads, D).permute(2, 0, 3, 4, 1).unbind(0)             # [B, h, d, N] views
+    s = F.normalize(q.float(), dim=-1) @ F.normalize(k.float(), dim=-1).transpose(-2, -1)
+    att = (torch.softmax(s * temperature.float().reshape(heads, 1, 1), -1).to(v.dtype) @ v)
+    return att.permute(0, 3, 1, 2).reshape(B, N, C)
