@@ -103,6 +103,9 @@ KERNEL_SIGNATURES = {
     "cgs_channel_attn_fwd": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
     "cgs_channel_attn_ws_bytes": [_I, _I, _I, _I],
     "cgs_channel_attn_chunk": [_I, _I, _I, _I],
+    # rectangular-window attention of DAT's spatial blocks (rect_attn.hip): qkv [B, H*W, 3C], o [B, H*W, C], the two
+    # branches' tables fp32 [(2 s0 - 1)(2 s1 - 1), heads / 2], scale, B, H, W, heads, D, s0, s1, shifted, stream
+    "cgs_rect_attn_fwd": [_P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     # narrow-K linear with optional fused LayerNorm (gemm_narrow.hip): x, lda, w, bias, gamma, beta, eps, ln, res, ldr,
     # y, ldc, M, N, K, CgsAct code, stream; row LayerNorm for C % 4 == 0: x, y, w, b, res, rows, C, eps, stream
     "cgs_gemm_narrow": [_P, _L, _P, _P, _P, _P, _F, _I, _P, _L, _P, _L, _L, _I, _I, _I, _P],

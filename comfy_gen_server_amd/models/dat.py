@@ -3,7 +3,8 @@ architecture/DAT.py:897-1182``). Residual groups alternate two block kinds:
 
 * spatial blocks: the channels are split in half, each half attends inside rectangular windows
   (``split_size`` and its transpose) with a dynamic (MLP-generated) relative position bias and
-  periodic half-window shifts; a depthwise-conv branch on V is mixed in through the adaptive
+  periodic half-window shifts (``ops.rect_window_attention`` on the packed qkv, ``CGS_RECT_ATTN``);
+  a depthwise-conv branch on V is mixed in through the adaptive
   interaction module (channel map from the conv branch, spatial map from the attention branch);
 * channel blocks: transposed (d x d) attention per head with a learned temperature
   (``ops.channel_attention`` on the packed qkv, ``CGS_CHANNEL_ATTN``), mixed with the same conv
@@ -11,7 +12,7 @@ architecture/DAT.py:897-1182``). Residual groups alternate two block kinds:
 
 each followed by the spatial-gate feed-forward (SGFN). Projections are ``layers.Linear``, dense
 convs ``layers.Conv2d``; depthwise convs and BatchNorm stay on torch modules. Shift masks and
-position tables are derived from the geometry (cached), not read from the file.
+position tables are derived from the geometry, not read from the file.
 """
 from __future__ import annotations
 
@@ -25,28 +26,6 @@ import torch.nn.functional as F
 from .. import ops
 from .layers import Conv2d, LayerNorm, Linear
 from .swin_sr import _resi_conv, _Upsample, _to_img, _to_tokens
-
-_MASKS: dict = {}
-
-
-def _rect_mask(H, W, wh, ww, sh, sw, device):
-    """Shifted-window mask for ``wh x ww`` windows shifted by (sh, sw): [nW, N, N] of 0 / -100."""
-    key = (H, W, wh, ww, sh, sw, str(device))
-    m = _MASKS.get(key)
-    if m is None:
-        lab = torch.zeros(H, W)
-        cnt = 0
-        for hs in (slice(0, -wh), slice(-wh, -sh), slice(-sh, None)):
-            for ws in (slice(0, -ww), slice(-ww, -sw), slice(-sw, None)):
-                lab[hs, ws] = cnt
-                cnt += 1
-        win = lab.view(H // wh, wh, W // ww, ww).permute(0, 2, 1, 3).reshape(-1, wh * ww)
-        d = win[:, None, :] - win[:, :, None]
-        m = torch.where(d != 0, torch.tensor(-100.0), torch.tensor(0.0)).to(device)
-        if len(_MASKS) > 64:
-            _MASKS.clear()
-        _MASKS[key] = m
-    return m
 
 
 class _DynPosBias(nn.Module):
@@ -63,7 +42,7 @@ class _DynPosBias(nn.Module):
 
 
 class _RectWindowAttention(nn.Module):
-    """One branch of the spatial block: attention in ``wh x ww`` windows over C/2 channels."""
+    """One branch of the spatial block (``wh x ww`` windows over C/2 channels): its position MLP and table."""
 
     def __init__(self, dim, heads, wh, ww):
         super().__init__()
@@ -74,24 +53,10 @@ class _RectWindowAttention(nn.Module):
         dw = torch.arange(1 - ww, ww)
         self.register_buffer("rpe_tab", torch.stack(torch.meshgrid(dh, dw, indexing="ij")).flatten(1).t().float(),
                              persistent=False)
-        c = torch.stack(torch.meshgrid(torch.arange(wh), torch.arange(ww), indexing="ij")).flatten(1)
-        r = (c[:, :, None] - c[:, None, :]).permute(1, 2, 0)
-        self.register_buffer("rel_idx", (r[..., 0] + wh - 1) * (2 * ww - 1) + (r[..., 1] + ww - 1), persistent=False)
 
-    def forward(self, q, k, v, H, W, mask):        # q/k/v [B, H, W, C] -> [B, H, W, C]
-        B, _, _, C = q.shape
-        wh, ww, h = self.wh, self.ww, self.heads
-        N = wh * ww
-
-        def win(t):
-            t = t.reshape(B, H // wh, wh, W // ww, ww, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, N, h, C // h)
-            return t.transpose(1, 2)
-
-        qw, kw, vw = win(q), win(k), win(v)
-        bias = self.pos(self.rpe_tab.to(self.pos.pos_proj.weight.dtype)).float()[self.rel_idx.reshape(-1)]
-        bias = bias.view(N, N, h).permute(2, 0, 1)
-        o = ops.attention_bias(qw, kw, vw, bias, mask, scale=self.scale).transpose(1, 2).reshape(-1, N, C)
-        return o.view(B, H // wh, W // ww, wh, ww, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
+    def table(self):
+        """The branch's relative-position table [(2wh-1)(2ww-1), heads], fp32, from the position MLP."""
+        return self.pos(self.rpe_tab.to(self.pos.pos_proj.weight.dtype)).float()
 
 
 def _aim_branches(dim):
@@ -115,27 +80,11 @@ class AdaptiveSpatialAttention(nn.Module):
 
     def forward(self, x, H, W):
         B, L, C = x.shape
-        qkv = self.qkv(x).view(B, H, W, 3, C)
-        v_img = qkv[..., 2, :].permute(0, 3, 1, 2)
-        m = max(self.split)
-        ph, pw = (m - H % m) % m, (m - W % m) % m
-        if ph or pw:
-            qkv = F.pad(qkv, (0, 0, 0, 0, 0, pw, 0, ph))
-        Hp, Wp = H + ph, W + pw
-        s0, s1 = self.shift
-        outs = []
-        for i, a in enumerate(self.attns):
-            t = qkv[..., C // 2:] if i else qkv[..., :C // 2]
-            shift = (s1, s0) if i else (s0, s1)
-            mask = None
-            if self.shifted:
-                t = torch.roll(t, (-shift[0], -shift[1]), (1, 2))
-                mask = _rect_mask(Hp, Wp, a.wh, a.ww, shift[0], shift[1], x.device)
-            o = a(t[..., 0, :], t[..., 1, :], t[..., 2, :], Hp, Wp, mask)
-            if self.shifted:
-                o = torch.roll(o, shift, (1, 2))
-            outs.append(o[:, :H, :W])
-        att = torch.cat(outs, -1).reshape(B, L, C)
+        qkv = self.qkv(x)
+        v_img = qkv.view(B, H, W, 3, C)[..., 2, :].permute(0, 3, 1, 2)
+        att = ops.rect_window_attention(qkv, (H, W), self.split, self.shifted, 2 * self.attns[0].heads,
+                                        [a.table() for a in self.attns], scale=self.attns[0].scale,
+                                        fused=ops.rect_window_attention_enabled(self.split))
         conv = self.dwconv(v_img.contiguous())
         cmap = self.channel_interaction(conv).view(B, 1, C)
         smap = self.spatial_interaction(_to_img(att, (H, W)))

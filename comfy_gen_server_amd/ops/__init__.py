@@ -18,6 +18,7 @@ from .core import (  # noqa: F401
     linear, linear_geglu, attention, attention_lse, attention_kv2, attention_bias, window_attention,
     window_attention_domain, window_attention_enabled, overlap_attention, overlap_attention_domain,
     overlap_attention_enabled, channel_attention, channel_attention_domain, channel_attention_enabled,
+    rect_window_attention, rect_window_attention_domain, rect_window_attention_enabled,
     narrow_linear, narrow_linear_domain, narrow_linear_enabled,
     group_norm, layer_norm, conv2d,
     conv2d_into, conv_slice_layout, conv_transpose2d, conv_transpose_phase_weights, silu, gelu, activation, ACT_CODES,

@@ -3205,3 +3205,128 @@ def channel_attention(qkv: torch.Tensor, heads: int, temperature: torch.Tensor, 
     s = F.normalize(q.float(), dim=-1) @ F.normalize(k.float(), dim=-1).transpose(-2, -1)
     att = (torch.softmax(s * temperature.float().reshape(heads, 1, 1), -1).to(v.dtype) @ v)
     return att.permute(0, 3, 1, 2).reshape(B, N, C)
+
+
+# Rectangular-window attention of DAT's spatial blocks (csrc/kernels/rect_attn.hip). CGS_RECT_ATTN=0 / 1 turns the
+# model's use of it off / on for every split; unset, the per-split default measured in profiles/r18/rect_attn.md holds
+# (the transposed splits were not measured and stay off).
+_RECT_SPLITS = ((8, 16), (16, 8), (8, 32), (32, 8))
+_RECT_ATTN_DEFAULT = {(8, 16): True, (8, 32): True, (16, 8): False, (32, 8): False}
+_RECT_MASKS: dict = {}
+_RECT_GEOM: dict = {}
+
+
+def rect_window_attention_enabled(split=None) -> bool:
+    """The model's switch; ``split`` None: whether every split of the domain is on."""
+    env = os.environ.get("CGS_RECT_ATTN")
+    if env is not None:
+        return env == "1"
+    if split is None:
+        return all(_RECT_ATTN_DEFAULT.values())
+    return _RECT_ATTN_DEFAULT.get(tuple(split), False)
+
+
+def rect_window_attention_domain(split, heads: int, D: int) -> bool:
+    """The shapes cgs_rect_attn_fwd takes (the device path also needs bf16 operands)."""
+    return tuple(split) in _RECT_SPLITS and heads >= 2 and heads % 2 == 0 and D % 2 == 0 and 2 <= D <= 32
+
+
+def _rect_mask(H, W, wh, ww, sh, sw, device):
+    """Shifted-window mask for ``wh x ww`` windows shifted by (sh, sw): [nW, N, N] of 0 / -100."""
+    key = (H, W, wh, ww, sh, sw, str(device))
+    m = _RECT_MASKS.get(key)
+    if m is None:
+        lab = torch.zeros(H, W)
+        cnt = 0
+        for hs in (slice(0, -wh), slice(-wh, -sh), slice(-sh, None)):
+            for ws in (slice(0, -ww), slice(-ww, -sw), slice(-sw, None)):
+                lab[hs, ws] = cnt
+                cnt += 1
+        win = lab.view(H // wh, wh, W // ww, ww).permute(0, 2, 1, 3).reshape(-1, wh * ww)
+        d = win[:, None, :] - win[:, :, None]
+        m = torch.where(d != 0, torch.tensor(-100.0), torch.tensor(0.0)).to(device)
+        if len(_RECT_MASKS) > 64:
+            _RECT_MASKS.clear()
+        _RECT_MASKS[key] = m
+    return m
+
+
+def _rect_rel_index(wh: int, ww: int, device) -> torch.Tensor:
+    """[N * N] index (yq - yk + wh-1)(2ww-1) + (xq - xk + ww-1) into a branch's table; cached."""
+    key = (wh, ww, str(device))
+    rel = _RECT_GEOM.get(key)
+    if rel is None:
+        c = torch.stack(torch.meshgrid(torch.arange(wh), torch.arange(ww), indexing="ij")).flatten(1)
+        r = (c[:, :, None] - c[:, None, :]).permute(1, 2, 0)
+        rel = _RECT_GEOM[key] = ((r[..., 0] + wh - 1) * (2 * ww - 1) + (r[..., 1] + ww - 1)).reshape(-1).to(device)
+    return rel
+
+
+def rect_window_attention(qkv: torch.Tensor, hw, split, shifted: bool, heads: int, tables, scale: float | None = None,
+                          fused: bool = True) -> torch.Tensor:
+    """The two-branch rectangular-window attention of DAT's spatial blocks on image-level tokens. Branch i (0, 1) owns
+    channels [i C/2, (i+1) C/2) of each of q, k, v (``heads`` / 2 heads) and attends, per window and head,
+
+        softmax(scale * q . k + tables[i][r(q, k), h] + m(q, k)) v       (fp32 scores and softmax)
+
+    in wh x ww = ``split`` (branch 0) or its transpose (branch 1) windows of the image zero-padded to multiples of
+    max(split) and, when ``shifted``, rolled by (-wh/2, -ww/2): r = (yq - yk + wh-1)(2ww-1) + (xq - xk + ww-1),
+    m = -100 between the regions the roll brings together. Padded tokens are zero q / k / v rows that stay in the
+    softmax as keys. ``qkv`` [B, H*W, 3*C], channel order [3][heads][D]; ``tables`` two fp32 [(2wh-1)(2ww-1), heads/2];
+    returns [B, H*W, C], both halves in place. bf16 on the GPU inside ``rect_window_attention_domain``: one launch of
+    cgs_rect_attn_fwd, which reads qkv in place (no pad, slice, roll, partition, bias or mask tensor). Elsewhere, and
+    with ``fused`` False (the model's switch, ``rect_window_attention_enabled``, off): the same function composed from
+    ``F.pad``, ``torch.roll``, the window partition, the table gather and ``attention_bias``."""
+    B, L, C3 = qkv.shape
+    H, W = hw
+    C = C3 // 3
+    h = heads // 2
+    D = C // heads
+    s0, s1 = int(split[0]), int(split[1])
+    R = (2 * s0 - 1) * (2 * s1 - 1)
+    if (fused and qkv.is_cuda and qkv.dtype == torch.bfloat16 and B > 0 and L == H * W and L > 0
+            and rect_window_attention_domain((s0, s1), heads, D) and C == heads * D
+            and all(tuple(t.shape) == (R, h) for t in tables)
+            and backend_for("rect_window_attention", qkv, "cgs_rect_attn_fwd") == "hip"):
+        qkv = qkv.contiguous()
+        t0, t1 = (t.float().contiguous() for t in tables)
+        o = torch.empty((B, L, C), device=qkv.device, dtype=qkv.dtype)
+        _check(_lib().cgs_rect_attn_fwd(qkv.data_ptr(), o.data_ptr(), t0.data_ptr(), t1.data_ptr(),
+                                        D ** -0.5 if scale is None else float(scale), B, H, W, heads, D, s0, s1,
+                                        1 if shifted else 0, _stream()), "cgs_rect_attn_fwd")
+        count("rect_window_attention", "hip")
+        count("attention", "hip")
+        return o
+    if qkv.device.type == "cpu":
+        count("rect_window_attention", "torch")
+    scale = (C // 2 // h) ** -0.5 if scale is None else scale
+    qkv = qkv.reshape(B, H, W, 3, C)
+    m = max(s0, s1)
+    ph, pw = (m - H % m) % m, (m - W % m) % m
+    if ph or pw:
+        qkv = F.pad(qkv, (0, 0, 0, 0, 0, pw, 0, ph))
+    Hp, Wp = H + ph, W + pw
+    outs = []
+    for i in range(2):
+        wh, ww = (s1, s0) if i else (s0, s1)
+        N, Cb = wh * ww, C // 2
+        t = qkv[..., C // 2:] if i else qkv[..., :C // 2]
+        shift = (wh // 2, ww // 2)
+        mask = None
+        if shifted:
+            t = torch.roll(t, (-shift[0], -shift[1]), (1, 2))
+            mask = _rect_mask(Hp, Wp, wh, ww, shift[0], shift[1], qkv.device)
+
+        def win(u):
+            u = u.reshape(B, Hp // wh, wh, Wp // ww, ww, Cb).permute(0, 1, 3, 2, 4, 5).reshape(-1, N, h, Cb // h)
+            return u.transpose(1, 2)
+
+        qw, kw, vw = win(t[..., 0, :]), win(t[..., 1, :]), win(t[..., 2, :])
+        bias = tables[i].float()[_rect_rel_index(wh, ww, qkv.device)]
+        bias = bias.view(N, N, h).permute(2, 0, 1)
+        o = attention_bias(qw, kw, vw, bias, mask, scale=scale).transpose(1, 2).reshape(-1, N, Cb)
+        o = o.view(B, Hp // wh, Wp // ww, wh, ww, Cb).permute(0, 1, 3, 2, 4, 5).reshape(B, Hp, Wp, Cb)
+        if shifted:
+            o = torch.roll(o, shift, (1, 2))
+        outs.append(o[:, :H, :W])
+    return torch.cat(outs, -1).reshape(B, L, C)
