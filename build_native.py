@@ -47,13 +47,14 @@ def _stale(src, obj, deps=()):
 # slower with identical results -- round 3 shipped one such v7 build -- so the build fails instead.
 SCRATCH_BUDGET = {"gemm_bf16_nt_v7_kernel": 128, "conv_nhwc_v7_kernel": 128, "attn_fwd_d64": 64,
                   "window_attn_kernel": 0, "gemm_narrow_kernel": 0, "overlap_attn_kernel": 0,
-                  "chan_gram_kernel": 0, "chan_softmax_kernel": 0, "chan_apply_kernel": 0, "rect_attn_kernel": 0}
+                  "chan_gram_kernel": 0, "chan_softmax_kernel": 0, "chan_apply_kernel": 0, "rect_attn_kernel": 0,
+                  "tok_dwconv3_kernel": 0, "aim_cmap_kernel": 0, "aim_mix_kernel": 0}
 
 # Extra compiler flags of single sources. window_attn.hip: no packed fp32 VALU ops (v_pk_add / mul / fma_f32) in its
-# score and softmax arithmetic, overlap_attn.hip, channel_attn.hip and rect_attn.hip likewise; gemm_narrow.hip: none in its LayerNorm and epilogue arithmetic.
+# score and softmax arithmetic, overlap_attn.hip, channel_attn.hip, rect_attn.hip and token_mix.hip likewise; gemm_narrow.hip: none in its LayerNorm and epilogue arithmetic.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"window_attn.hip": _NO_PK_F32, "gemm_narrow.hip": _NO_PK_F32, "overlap_attn.hip": _NO_PK_F32,
-               "channel_attn.hip": _NO_PK_F32, "rect_attn.hip": _NO_PK_F32}
+               "channel_attn.hip": _NO_PK_F32, "rect_attn.hip": _NO_PK_F32, "token_mix.hip": _NO_PK_F32}
 
 
 def _resources(out):

@@ -106,6 +106,13 @@ KERNEL_SIGNATURES = {
     # rectangular-window attention of DAT's spatial blocks (rect_attn.hip): qkv [B, H*W, 3C], o [B, H*W, C], the two
     # branches' tables fp32 [(2 s0 - 1)(2 s1 - 1), heads / 2], scale, B, H, W, heads, D, s0, s1, shifted, stream
     "cgs_rect_attn_fwd": [_P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    # depthwise 3 x 3 on token-major rows (token_mix.hip): x, pitch, w [C, 9], bias, BatchNorm gamma / beta / mean / var,
+    # eps, m, pitch, y, ws, ws bytes, pool_src, B, H, W, C, epilogue (0 plain, 1 BatchNorm + GELU, 2 multiply), stream
+    "cgs_token_dwconv3": [_P, _L, _P, _P, _P, _P, _P, _P, _F, _P, _L, _P, _P, _L, _P, _I, _I, _I, _I, _I, _P],
+    # DAT's adaptive interaction module (token_mix.hip): qkv, att, y, 22 parameter pointers, the three BatchNorm eps, ws,
+    # ws bytes, B, H, W, C, hc, hs, kind (0 spatial, 1 channel), stream; workspace bytes for (B, H, W, C)
+    "cgs_aim_fwd": [_P, _P, _P, _P, _F, _F, _F, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P],
+    "cgs_aim_ws_bytes": [_I, _I, _I, _I],
     # narrow-K linear with optional fused LayerNorm (gemm_narrow.hip): x, lda, w, bias, gamma, beta, eps, ln, res, ldr,
     # y, ldc, M, N, K, CgsAct code, stream; row LayerNorm for C % 4 == 0: x, y, w, b, res, rows, C, eps, stream
     "cgs_gemm_narrow": [_P, _L, _P, _P, _P, _P, _F, _I, _P, _L, _P, _L, _L, _I, _I, _I, _P],
@@ -276,7 +283,7 @@ KERNEL_SIGNATURES = {
 }
 
 
-_RESTYPE = {"cgs_channel_attn_ws_bytes": ctypes.c_longlong, "cgs_groupnorm_workspace": ctypes.c_longlong, "cgs_splitk_ws_bytes": ctypes.c_longlong, "cgs_groupnorm_f32_ws": ctypes.c_longlong, "cgs_grn_slices": ctypes.c_int, "cgs_v7_ws_bytes": ctypes.c_longlong, "cgs_gemm_skinny_ws_bytes": ctypes.c_longlong, "cgs_gemm_set_variant": None, "cgs_v7_set_dbg": None, "cgs_v6_set_mode": None, "cgs_attn_set_prio": None, "cgs_gn_set_blocks": None, "cgs_conv_smalln_set_lds": None, "cgs_attn_set_kv2_rows": None, "cgs_grn_set_rows": None,
+_RESTYPE = {"cgs_channel_attn_ws_bytes": ctypes.c_longlong, "cgs_aim_ws_bytes": ctypes.c_longlong, "cgs_groupnorm_workspace": ctypes.c_longlong, "cgs_splitk_ws_bytes": ctypes.c_longlong, "cgs_groupnorm_f32_ws": ctypes.c_longlong, "cgs_grn_slices": ctypes.c_int, "cgs_v7_ws_bytes": ctypes.c_longlong, "cgs_gemm_skinny_ws_bytes": ctypes.c_longlong, "cgs_gemm_set_variant": None, "cgs_v7_set_dbg": None, "cgs_v6_set_mode": None, "cgs_attn_set_prio": None, "cgs_gn_set_blocks": None, "cgs_conv_smalln_set_lds": None, "cgs_attn_set_kv2_rows": None, "cgs_grn_set_rows": None,
             "cgs_conv_set_variant": None, "cgs_set_tile_group": None, "cgs_conv_set_tile_group": None, "cgs_dwconv_set_px": None, "cgs_upconv_set_tile_group": None,
             "cgs_attn_set_variant": None,
             "cgs_conv_v6_set_loader": None}

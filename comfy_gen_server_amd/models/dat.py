@@ -5,13 +5,15 @@ architecture/DAT.py:897-1182``). Residual groups alternate two block kinds:
   (``split_size`` and its transpose) with a dynamic (MLP-generated) relative position bias and
   periodic half-window shifts (``ops.rect_window_attention`` on the packed qkv, ``CGS_RECT_ATTN``);
   a depthwise-conv branch on V is mixed in through the adaptive
-  interaction module (channel map from the conv branch, spatial map from the attention branch);
+  interaction module (channel map from the conv branch, spatial map from the attention branch;
+  ``ops.adaptive_interaction``, ``CGS_DAT_AIM``);
 * channel blocks: transposed (d x d) attention per head with a learned temperature
   (``ops.channel_attention`` on the packed qkv, ``CGS_CHANNEL_ATTN``), mixed with the same conv
   branch the other way round;
 
-each followed by the spatial-gate feed-forward (SGFN). Projections are ``layers.Linear``, dense
-convs ``layers.Conv2d``; depthwise convs and BatchNorm stay on torch modules. Shift masks and
+each followed by the spatial-gate feed-forward (SGFN; its gate conv is ``ops.token_dwconv3x3``,
+``CGS_DAT_SGATE``). Projections are ``layers.Linear``, dense convs ``layers.Conv2d``; the depthwise convs and
+BatchNorms stay torch modules as parameter holders, which the two ops read or, switched off, call. Shift masks and
 position tables are derived from the geometry, not read from the file.
 """
 from __future__ import annotations
@@ -59,11 +61,12 @@ class _RectWindowAttention(nn.Module):
         return self.pos(self.rpe_tab.to(self.pos.pos_proj.weight.dtype)).float()
 
 
-def _aim_branches(dim):
+def _aim_branches(dim, hc=None, hs=None):
+    """The parameter holders of the adaptive interaction module; hidden widths ``hc`` / ``hs`` default to dim / 8, / 16."""
+    hc, hs = hc or dim // 8, hs or dim // 16
     dw = nn.Sequential(nn.Conv2d(dim, dim, 3, padding=1, groups=dim), nn.BatchNorm2d(dim), nn.GELU())
-    ci = nn.Sequential(nn.AdaptiveAvgPool2d(1), Conv2d(dim, dim // 8, 1), nn.BatchNorm2d(dim // 8), nn.GELU(),
-                       Conv2d(dim // 8, dim, 1))
-    si = nn.Sequential(Conv2d(dim, dim // 16, 1), nn.BatchNorm2d(dim // 16), nn.GELU(), Conv2d(dim // 16, 1, 1))
+    ci = nn.Sequential(nn.AdaptiveAvgPool2d(1), Conv2d(dim, hc, 1), nn.BatchNorm2d(hc), nn.GELU(), Conv2d(hc, dim, 1))
+    si = nn.Sequential(Conv2d(dim, hs, 1), nn.BatchNorm2d(hs), nn.GELU(), Conv2d(hs, 1, 1))
     return dw, ci, si
 
 
@@ -81,16 +84,12 @@ class AdaptiveSpatialAttention(nn.Module):
     def forward(self, x, H, W):
         B, L, C = x.shape
         qkv = self.qkv(x)
-        v_img = qkv.view(B, H, W, 3, C)[..., 2, :].permute(0, 3, 1, 2)
         att = ops.rect_window_attention(qkv, (H, W), self.split, self.shifted, 2 * self.attns[0].heads,
                                         [a.table() for a in self.attns], scale=self.attns[0].scale,
                                         fused=ops.rect_window_attention_enabled(self.split))
-        conv = self.dwconv(v_img.contiguous())
-        cmap = self.channel_interaction(conv).view(B, 1, C)
-        smap = self.spatial_interaction(_to_img(att, (H, W)))
-        att = att * torch.sigmoid(cmap)
-        conv = (torch.sigmoid(smap) * conv).flatten(2).transpose(1, 2)
-        return self.proj(att + conv)
+        return self.proj(ops.adaptive_interaction(
+            qkv, att, (H, W), (self.dwconv, self.channel_interaction, self.spatial_interaction), "spatial",
+            fused=ops.adaptive_interaction_enabled()))
 
 
 class AdaptiveChannelAttention(nn.Module):
@@ -107,13 +106,9 @@ class AdaptiveChannelAttention(nn.Module):
         h = self.heads
         qkv = self.qkv(x)
         att = ops.channel_attention(qkv, h, self.temperature, fused=ops.channel_attention_enabled())
-        v = qkv.view(B, N, 3, h, C // h)[:, :, 2].permute(0, 2, 3, 1)                # [B, h, d, N]
-        conv = self.dwconv(v.reshape(B, C, H, W))
-        cmap = self.channel_interaction(_to_img(att, (H, W)))
-        smap = self.spatial_interaction(conv).flatten(2).transpose(1, 2)             # [B, N, 1]
-        att = att * torch.sigmoid(smap)
-        conv = (conv * torch.sigmoid(cmap)).flatten(2).transpose(1, 2)
-        return self.proj(att + conv)
+        return self.proj(ops.adaptive_interaction(
+            qkv, att, (H, W), (self.dwconv, self.channel_interaction, self.spatial_interaction), "channel",
+            fused=ops.adaptive_interaction_enabled()))
 
 
 class _SpatialGate(nn.Module):
@@ -124,8 +119,8 @@ class _SpatialGate(nn.Module):
 
     def forward(self, x, H, W):
         a, g = x.chunk(2, -1)
-        g = self.conv(_to_img(self.norm(g), (H, W)).contiguous())
-        return a * _to_tokens(g)
+        return ops.token_dwconv3x3(self.norm(g), (H, W), self.conv.weight, self.conv.bias, mul=a,
+                                   fused=ops.token_dwconv_enabled())
 
 
 class _SGFN(nn.Module):

@@ -20,6 +20,8 @@ from .core import (  # noqa: F401
     overlap_attention_enabled, channel_attention, channel_attention_domain, channel_attention_enabled,
     rect_window_attention, rect_window_attention_domain, rect_window_attention_enabled,
     narrow_linear, narrow_linear_domain, narrow_linear_enabled,
+    token_dwconv3x3, token_dwconv_enabled, adaptive_interaction, adaptive_interaction_domain,
+    adaptive_interaction_enabled,
     group_norm, layer_norm, conv2d,
     conv2d_into, conv_slice_layout, conv_transpose2d, conv_transpose_phase_weights, silu, gelu, activation, ACT_CODES,
     upsample_nearest2x, timestep_embedding, cfg_combine, euler_step, depthwise_conv2d_nhwc,

@@ -9,6 +9,7 @@ Tensor conventions
 from __future__ import annotations
 
 import collections
+import ctypes
 import math
 import os
 
@@ -3330,3 +3331,165 @@ def rect_window_attention(qkv: torch.Tensor, hw, split, shifted: bool, heads: in
             o = torch.roll(o, shift, (1, 2))
         outs.append(o[:, :H, :W])
     return torch.cat(outs, -1).reshape(B, L, C)
+
+
+# Token-layout depthwise 3 x 3 conv and the adaptive interaction module (AIM) of DAT (csrc/kernels/token_mix.hip).
+# CGS_DAT_AIM=0 / 1 turns the model's use of the fused AIM off / on, CGS_DAT_SGATE=0 / 1 that of the fused spatial gate
+# of its feed-forward; unset, the defaults of profiles/r19/aim.md hold.
+_DAT_AIM_DEFAULT = True
+_DAT_SGATE_DEFAULT = True
+_AIM_KINDS = {"spatial": 0, "channel": 1}
+
+
+def adaptive_interaction_enabled() -> bool:
+    env = os.environ.get("CGS_DAT_AIM")
+    return _DAT_AIM_DEFAULT if env is None else env == "1"
+
+
+def token_dwconv_enabled() -> bool:
+    env = os.environ.get("CGS_DAT_SGATE")
+    return _DAT_SGATE_DEFAULT if env is None else env == "1"
+
+
+def adaptive_interaction_domain(C: int, hc: int, hs: int) -> bool:
+    """The shapes cgs_aim_fwd takes (the device path also needs bf16 operands and parameters)."""
+    return C % 4 == 0 and 16 <= C <= 256 and 1 <= hc <= 32 and 1 <= hs <= 16
+
+
+def _token_rows(t, B, N, C):
+    """Pixel pitch (elements) of ``t`` [B, N, C] if it is token rows the kernels can read in place -- contiguous, or a
+    last-dimension slice of wider contiguous rows, 8-byte aligned -- else None."""
+    if t.dim() != 3 or tuple(t.shape) != (B, N, C) or t.stride(2) != 1:
+        return None
+    pitch = t.stride(1)
+    if pitch < C or pitch % 4 or (B > 1 and t.stride(0) != N * pitch) or t.data_ptr() % 8:
+        return None
+    return pitch
+
+
+def _bn_values(bn):
+    """(weight, bias, mean, var, eps) of an eval-mode BatchNorm2d or of the five values themselves."""
+    if isinstance(bn, torch.nn.Module):
+        return None if bn.training else (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+    return tuple(bn)
+
+
+def _dev_bf16(x, *ts):
+    return all(t is not None and t.dtype == torch.bfloat16 and t.device == x.device and t.is_contiguous() for t in ts)
+
+
+def token_dwconv3x3(x: torch.Tensor, hw, weight: torch.Tensor, bias: torch.Tensor | None, *, bn=None,
+                    act: str | None = None, mul: torch.Tensor | None = None, fused: bool = True) -> torch.Tensor:
+    """Depthwise 3 x 3 conv (stride 1, zero padding) of the H x W image whose pixels are the token rows of ``x``
+    [B, H*W, C], with an optional epilogue: ``bn`` (an eval-mode ``BatchNorm2d`` or its (weight, bias, mean, var,
+    eps)) and ``act="gelu"`` together, or ``mul`` [B, H*W, C], y = mul * conv. ``x`` and ``mul`` may be last-dimension
+    slices of wider rows (the v third of a packed qkv, a half of the SGFN's hidden rows); ``weight`` is [C, 1, 3, 3].
+    Returns [B, H*W, C]. bf16 on the GPU with C % 4 == 0: one launch of cgs_token_dwconv3, which reads the rows where
+    they lie (no NCHW copy). Elsewhere, and with ``fused`` False (the model's switch, ``token_dwconv_enabled``, off):
+    ``F.conv2d(groups=C)`` on the NCHW copy, BatchNorm, GELU, and the product on the transposed view."""
+    B, N, C = x.shape
+    H, W = hw
+    bnv = None if bn is None else _bn_values(bn)
+    epi = 0 if bn is None and act is None and mul is None else 1 if bnv is not None and act == "gelu" and mul is None \
+        else 2 if bn is None and act is None else None
+    if (fused and epi is not None and x.is_cuda and x.dtype == torch.bfloat16 and N == H * W and N > 0 and B > 0
+            and C % 4 == 0 and C > 0 and tuple(weight.shape) == (C, 1, 3, 3) and _dev_bf16(x, weight)
+            and (bias is None or _dev_bf16(x, bias)) and (epi != 1 or _dev_bf16(x, *bnv[:4]))
+            and backend_for("token_dwconv3x3", x, "cgs_token_dwconv3") == "hip"):
+        xp = _token_rows(x, B, N, C)
+        if xp is None:
+            x = x.contiguous()
+            xp = C
+        mp = 0
+        if mul is not None:
+            mp = _token_rows(mul, B, N, C) if mul.dtype == x.dtype and mul.device == x.device else None
+            if mp is None:
+                mul = mul.to(x.dtype).expand(B, N, C).contiguous()
+                mp = C
+        if B * N * max(xp, mp) < 2 ** 31:
+            y = torch.empty((B, N, C), device=x.device, dtype=x.dtype)
+            b4 = [None] * 4 if epi != 1 else [t.data_ptr() for t in bnv[:4]]
+            _check(_lib().cgs_token_dwconv3(x.data_ptr(), xp, weight.data_ptr(), _ptr(bias), *b4,
+                                            float(bnv[4]) if epi == 1 else 0.0, _ptr(mul), mp, y.data_ptr(), None, 0,
+                                            None, B, H, W, C, epi, _stream()), "cgs_token_dwconv3")
+            count("token_dwconv3x3", "hip")
+            return y
+    if x.device.type == "cpu":
+        count("token_dwconv3x3", "torch")
+    y = F.conv2d(x.transpose(1, 2).reshape(B, C, H, W).contiguous(), weight, bias, 1, 1, 1, C)
+    if bn is not None:
+        y = bn(y) if isinstance(bn, torch.nn.Module) else F.batch_norm(y, bnv[2], bnv[3], bnv[0], bnv[1], False, 0.0,
+                                                                     bnv[4])
+    if act is not None:
+        if act != "gelu":
+            raise ValueError(f"token_dwconv3x3: act {act!r} (only 'gelu')")
+        y = F.gelu(y)
+    y = y.flatten(2).transpose(1, 2)
+    return y if mul is None else mul * y
+
+
+def _aim_tensors(params):
+    """The 22 tensors of cgs_aim_fwd's parameter table and the three BatchNorm eps, from the module triple."""
+    dw, ci, si = params
+
+    def bn(m):
+        return (m.weight, m.bias, m.running_mean, m.running_var)
+    return ((dw[0].weight, dw[0].bias, *bn(dw[1]), ci[1].weight, ci[1].bias, *bn(ci[2]), ci[4].weight, ci[4].bias,
+             si[0].weight, si[0].bias, *bn(si[1]), si[3].weight, si[3].bias), (dw[1].eps, ci[2].eps, si[1].eps))
+
+
+def adaptive_interaction(qkv: torch.Tensor, att: torch.Tensor, hw, params, kind: str, fused: bool = True) -> torch.Tensor:
+    """The adaptive interaction module of DAT between an attention and its output projection. With v the last third of
+    ``qkv`` [B, H*W, 3C] seen as an H x W image and ``att`` [B, H*W, C] the attention output,
+
+        conv = gelu(bn(dwconv3x3(v)))
+        kind "spatial":  y = att * sigmoid(ci(pool(conv))) + conv * sigmoid(si(att))
+        kind "channel":  y = att * sigmoid(si(conv)) + conv * sigmoid(ci(pool(att)))
+
+    where ci = 1x1 conv, BatchNorm, GELU, 1x1 conv on the global average pool (a gate a channel) and si the same on
+    every token down to one value (a gate a token). ``params`` is the block's (dwconv, channel_interaction,
+    spatial_interaction) triple of eval-mode modules; their tensors are read where they lie, the hidden widths come
+    from the weight shapes. Returns [B, H*W, C], the tensor ``proj`` reads. bf16 on the GPU inside
+    ``adaptive_interaction_domain``: three launches of cgs_aim_fwd (no NCHW copy, pool, gate or product tensor).
+    Elsewhere, and with ``fused`` False (the model's switch, ``adaptive_interaction_enabled``, off): the modules
+    composed as DAT's blocks composed them."""
+    B, N, C3 = qkv.shape
+    H, W = hw
+    C = C3 // 3
+    dw, ci, si = params
+    code = _AIM_KINDS[kind]
+    if (fused and qkv.is_cuda and qkv.dtype == torch.bfloat16 and att.dtype == qkv.dtype and B > 0 and N == H * W
+            and N > 0 and C3 == 3 * C and tuple(att.shape) == (B, N, C) and 3 * B * N * C < 2 ** 31
+            and not (dw.training or ci.training or si.training)
+            and backend_for("adaptive_interaction", qkv, "cgs_aim_fwd") == "hip"):
+        ts, eps = _aim_tensors(params)
+        hc, hs = ts[6].shape[0], ts[14].shape[0]
+        if adaptive_interaction_domain(C, hc, hs) and _dev_bf16(qkv, *ts) and tuple(ts[0].shape) == (C, 1, 3, 3) \
+                and ts[6].numel() == hc * C and ts[12].numel() == C * hc and ts[14].numel() == hs * C \
+                and ts[20].numel() == hs:
+            qkv, att = qkv.contiguous(), att.contiguous()
+            nbytes = int(_lib().cgs_aim_ws_bytes(B, H, W, C))
+            ws = torch.empty(nbytes, device=qkv.device, dtype=torch.uint8)
+            y = torch.empty((B, N, C), device=qkv.device, dtype=qkv.dtype)
+            ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+            _check(_lib().cgs_aim_fwd(qkv.data_ptr(), att.data_ptr(), y.data_ptr(), ptrs, *map(float, eps),
+                                      ws.data_ptr(), nbytes, B, H, W, C, hc, hs, code, _stream()), "cgs_aim_fwd")
+            count("adaptive_interaction", "hip")
+            return y
+    if qkv.device.type == "cpu":
+        count("adaptive_interaction", "torch")
+    if code == 0:
+        v_img = qkv.view(B, H, W, 3, C)[..., 2, :].permute(0, 3, 1, 2)
+        conv = dw(v_img.contiguous())
+        cmap = ci(conv).view(B, 1, C)
+        smap = si(att.transpose(1, 2).reshape(B, C, H, W))
+        att = att * torch.sigmoid(cmap)
+        conv = (torch.sigmoid(smap) * conv).flatten(2).transpose(1, 2)
+        return att + conv
+    v = qkv.view(B, N, 3, C)[:, :, 2].permute(0, 2, 1)
+    conv = dw(v.reshape(B, C, H, W))
+    cmap = ci(att.transpose(1, 2).reshape(B, C, H, W))
+    smap = si(conv).flatten(2).transpose(1, 2)             # [B, N, 1]
+    att = att * torch.sigmoid(smap)
+    conv = (conv * torch.sigmoid(cmap)).flatten(2).transpose(1, 2)
+    return att + conv
